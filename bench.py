@@ -9,13 +9,20 @@ halo exchange -> K4 full LLH + scalar allreduce) — exactly the reference's
 Default config: com-Amazon-shaped synthetic power-law graph (335k nodes /
 926k undirected edges — the real dataset is a missing blob upstream),
 K=5000, random-init F.  The graph is global and fixed as GPUs are added
-(row-sharded) -> strong scaling.  Both compute dtypes are measured every
-run: the headline number is bf16 (fp32 accumulation everywhere — grad,
-sumF, LLH in fp64) and the fp32-storage number is emitted alongside in
-``variants`` so neither can be read as a precision-assisted claim.
+(row-sharded) -> strong scaling.  The headline number is bf16 (fp32
+accumulation everywhere — grad, sumF, LLH in fp64).
+
+A plain run does only what the headline figure needs: set up, warm up,
+time ``--steps`` sweeps, print the JSON result line.  ``--full`` adds the
+second-dtype measurement (fp32 storage when the headline is bf16), emitted
+alongside in ``variants`` so neither number can be read as a
+precision-assisted claim.  ``--dump-outputs DIR`` writes what the last
+timed sweep returned (see ``_collect_outputs``) as ``DIR/<name>.npy``;
+graph and init are seeded, so two builds run with the same arguments see
+identical inputs and can be compared output for output.
 
 Run (driver contract):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   torchrun --nnodes=1 --nproc-per-node N bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -35,10 +42,62 @@ from bigclam.io import shaped_graph
 from bigclam.utils.metrics import MetricsLogger
 
 
-def _time_sweeps(graph, dtype, args, rank, world, device, use_cuda):
+_DUMP_MATRIX_BYTES = 20 << 20  # per sampled [rows, K] fp32 matrix
+_DUMP_VECTOR_ELEMS = 1 << 20  # per per-node vector
+
+
+def _sample(n, max_n):
+    """Fixed, seeded, sorted subset of range(n) (all of it when it fits)."""
+    if n <= max_n:
+        return np.arange(n, dtype=np.int64)
+    rng = np.random.default_rng(12345)
+    return np.sort(rng.choice(n, size=max_n, replace=False)).astype(np.int64)
+
+
+def _collect_outputs(tr, carry, llh, steps):
+    """What the last timed ``pipelined_sweep`` handed back, as host
+    float32/float64 arrays (this rank's rows), bounded to well under 64 MB:
+
+      llh          [1]  f64  global objective after the committed step
+      steps        [n]  f32  step sizes the sweep committed
+      steps_next   [n]  f32  carry: line-search result for the next commit
+      grad_rows    [r,K] f32 carry: gradient, on a seeded row sample (rows
+                             the sparse kernel handled carry their gradient
+                             in compact form and are written as zeros)
+      F_rows       [r,K] f32 the model after the commit, same row sample
+      sumF         [K]  f32  its column sums
+      vector_rows / matrix_rows  f64  the node ids of the sampled entries
+    """
+    grad, steps_next, pack = carry
+    st = tr.state
+    n, k = st.n_local, tr.cfg.k
+    vrows = _sample(n, _DUMP_VECTOR_ELEMS)
+    mrows = _sample(n, max(1, _DUMP_MATRIX_BYTES // (4 * k)))
+    vsel = torch.from_numpy(vrows).to(steps.device)
+    msel = torch.from_numpy(mrows).to(steps.device)
+    g = grad[msel, :k].float()
+    if pack is not None:
+        routed = torch.zeros(n, dtype=torch.bool, device=g.device)
+        routed[pack["order"].long()] = True
+        g[routed[msel]] = 0.0
+    return {
+        "llh": np.asarray([llh], dtype=np.float64),
+        "steps": steps[vsel].float().cpu().numpy(),
+        "steps_next": steps_next[vsel].float().cpu().numpy(),
+        "grad_rows": g.cpu().numpy(),
+        "F_rows": st.F_local_k[msel].float().cpu().numpy(),
+        "sumF": st.sumF[:k].float().cpu().numpy(),
+        "vector_rows": vrows.astype(np.float64),
+        "matrix_rows": mrows.astype(np.float64),
+    }
+
+
+def _time_sweeps(graph, dtype, args, rank, world, device, use_cuda,
+                 collect=False):
     """Build a trainer at ``dtype`` and time ``args.steps`` pipelined
     sweeps after ``args.warmup`` untimed ones.  Returns (elapsed_s, value,
-    ms_per_step) with elapsed = MAX over ranks."""
+    ms_per_step, outputs) with elapsed = MAX over ranks; ``outputs`` is
+    ``_collect_outputs`` of the last timed sweep when ``collect``."""
     cfg = BigClamConfig(
         k=args.k,
         dtype=dtype,
@@ -66,11 +125,15 @@ def _time_sweeps(graph, dtype, args, rank, world, device, use_cuda):
     comm.barrier()
     sync()
     t0 = time.perf_counter()
+    llh = steps = None
     for _ in range(args.steps):
-        carry, _, _ = tr.pipelined_sweep(carry)
+        carry, llh, steps = tr.pipelined_sweep(carry)
     comm.barrier()
     sync()
     elapsed = time.perf_counter() - t0
+    outputs = None
+    if collect and steps is not None:
+        outputs = _collect_outputs(tr, carry, llh, steps)
 
     # max over ranks
     el = torch.tensor(
@@ -88,7 +151,7 @@ def _time_sweeps(graph, dtype, args, rank, world, device, use_cuda):
     del tr
     if use_cuda:
         torch.cuda.empty_cache()
-    return elapsed, edges_per_sec, ms_per_step
+    return elapsed, edges_per_sec, ms_per_step, outputs
 
 
 def main():
@@ -104,9 +167,17 @@ def main():
     ap.add_argument("--locality", type=float, default=0.7)
     ap.add_argument("--ls-steps", type=int, default=15,
                     help="Armijo ladder depth (reference: 15 -> 16 candidates)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure (the second-dtype variant)")
     ap.add_argument("--no-variant", action="store_true",
-                    help="skip the second-dtype measurement")
+                    help="with --full: skip the second-dtype measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed sweep's outputs as "
+                         "DIR/<name>.npy (rank 0's rows)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     rank = comm.init_distributed()
     world = comm.get_world_size()
@@ -116,14 +187,20 @@ def main():
     graph = shaped_graph(
         args.nodes, args.edges, locality=args.locality, seed=args.graph_seed
     )
-    _, value, ms_per_step = _time_sweeps(
-        graph, args.dtype, args, rank, world, device, use_cuda
+    _, value, ms_per_step, outputs = _time_sweeps(
+        graph, args.dtype, args, rank, world, device, use_cuda,
+        collect=args.dump_outputs is not None,
     )
+    if outputs is not None and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+    del outputs
     variants = {}
-    if not args.no_variant:
+    if args.full and not args.no_variant:
         other = "fp32" if args.dtype == "bf16" else "bf16"
         try:
-            _, v2, ms2 = _time_sweeps(
+            _, v2, ms2, _ = _time_sweeps(
                 graph, other, args, rank, world, device, use_cuda
             )
             variants[other] = {"value": v2, "ms_per_step": ms2}

@@ -130,6 +130,84 @@ def test_cli_bench_delegates(capfd):
     assert "parallelism" in rec["config"] and "k" in rec["config"]
 
 
+_BENCH_TINY = [
+    "bench", "--steps", "2", "--warmup", "1", "--nodes", "400",
+    "--edges", "1200", "--k", "16",
+]
+
+
+def test_bench_plain_vs_full(capfd):
+    """A plain run measures the headline dtype only; --full adds the
+    second-dtype variant next to it."""
+    import json as _json
+
+    from bigclam.cli import main
+
+    main(_BENCH_TINY)
+    plain = _json.loads(capfd.readouterr().out.strip().splitlines()[-1])
+    assert plain["variants"] == {}
+    assert plain["steps"] == 2 and plain["ms_per_step"] > 0
+    main(_BENCH_TINY + ["--full"])
+    full = _json.loads(capfd.readouterr().out.strip().splitlines()[-1])
+    assert full["dtype"] == plain["dtype"] == "bf16"
+    assert full["variants"]["fp32"]["value"] > 0
+    assert full["variants"]["fp32"]["ms_per_step"] > 0
+
+
+def test_bench_dump_outputs(tmp_path, capfd, monkeypatch):
+    """--dump-outputs writes the last timed sweep's arrays as float .npy
+    files, identical from run to run (seeded graph + init), and they are
+    the outputs of exactly --steps sweeps after --warmup.  Pinned to the
+    CPU path (also on a GPU box) so the hand-driven run below is
+    bit-comparable."""
+    import numpy as np
+    import torch
+
+    from bigclam.cli import main
+    from bigclam.config import BigClamConfig
+    from bigclam.engine.trainer import Trainer
+    from bigclam.io import shaped_graph
+
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    args = _BENCH_TINY + ["--dtype", "fp32"]
+    a, b = tmp_path / "a", tmp_path / "b"
+    main(args + ["--dump-outputs", str(a)])
+    main(args + ["--dump-outputs", str(b)])
+    capfd.readouterr()
+    names = sorted(p.name for p in a.iterdir())
+    assert names == sorted(p.name for p in b.iterdir())
+    assert {"llh.npy", "steps.npy", "steps_next.npy", "grad_rows.npy",
+            "F_rows.npy", "sumF.npy"} <= set(names)
+    total = 0
+    for n in names:
+        x, y = np.load(a / n), np.load(b / n)
+        assert x.dtype in (np.float32, np.float64)
+        assert np.isfinite(x).all()
+        np.testing.assert_array_equal(x, y)
+        total += x.nbytes
+    assert total <= 64 << 20
+
+    # the same 1 warmup + 2 timed sweeps, driven by hand
+    g = shaped_graph(400, 1200, locality=0.7, seed=42)
+    cfg = BigClamConfig(k=16, dtype="fp32", device="cpu", seed=7)
+    tr = Trainer(g, cfg, rank=0, world_size=1, device=torch.device("cpu"))
+    tr.init_F("random")
+    carry, _ = tr.prologue()
+    for _ in range(3):
+        carry, llh, steps = tr.pipelined_sweep(carry)
+    rows = np.load(a / "matrix_rows.npy").astype(np.int64)
+    vrows = np.load(a / "vector_rows.npy").astype(np.int64)
+    assert np.load(a / "llh.npy")[0] == llh
+    np.testing.assert_array_equal(np.load(a / "steps.npy"),
+                                  steps.numpy()[vrows])
+    np.testing.assert_array_equal(np.load(a / "steps_next.npy"),
+                                  carry[1].numpy()[vrows])
+    np.testing.assert_array_equal(np.load(a / "grad_rows.npy"),
+                                  carry[0].numpy()[rows][:, :16])
+    np.testing.assert_array_equal(np.load(a / "F_rows.npy"),
+                                  tr.state.F_local_k.numpy()[rows])
+
+
 def test_cli_fit_resume(tmp_path):
     """CLI --resume continues a checkpointed fit: the resumed run picks up
     the saved sweep/llh and matches an uninterrupted run's final LLH."""

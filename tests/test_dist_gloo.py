@@ -158,8 +158,11 @@ def test_torchrun_bench_cpu(tmp_path):
         "--gpus", "2", "--steps", "2", "--warmup", "1",
         "--k", "8", "--nodes", "300", "--edges", "900", "--dtype", "fp32",
     ]
+    # CPU/gloo by construction: hide any GPUs from the ranks (on a GPU box
+    # bench.py would otherwise pick RCCL and one device per local rank)
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     out = subprocess.run(
-        cmd, capture_output=True, text=True, timeout=300, cwd=root
+        cmd, capture_output=True, text=True, timeout=300, cwd=root, env=env
     )
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]

@@ -95,33 +95,54 @@ def test_shaped_graph_exact_counts():
 import os
 import pytest as _pytest
 
-_REF_DATA = "/root/reference/data"
+_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-@_pytest.mark.skipif(
-    not os.path.isdir(_REF_DATA), reason="reference datasets not mounted"
-)
-def test_parse_reference_datasets():
+@_pytest.fixture(scope="session")
+def snap_files(tmp_path_factory):
+    """The two SNAP datasets the reference ships, re-materialized as
+    edge-list text from the stored edge arrays (tests/golden/*.edges.npz:
+    every line of the original files, in file order, as uint16 id pairs).
+    Email-Enron keeps its '#' header, tab separators and CRLF line ends;
+    facebook_combined is space-separated with no header."""
+    import numpy as np
+
+    d = tmp_path_factory.mktemp("snap")
+    enron = np.load(os.path.join(_GOLDEN, "Email-Enron.edges.npz"))["edges"]
+    with open(d / "Email-Enron.txt", "w", newline="") as f:
+        f.write(
+            "# Directed graph (each unordered pair of nodes is saved once): "
+            "Email-Enron.txt \r\n"
+            "# Enron email network (edge indicated that email was exchanged, "
+            "undirected edges)\r\n"
+            "# Nodes: 36692 Edges: 367662\r\n"
+            "# FromNodeId\tToNodeId\r\n"
+        )
+        f.write("".join(f"{a}\t{b}\r\n" for a, b in enron.tolist()))
+    fb = np.load(os.path.join(_GOLDEN, "facebook_combined.edges.npz"))["edges"]
+    with open(d / "facebook_combined.txt", "w", newline="") as f:
+        f.write("".join(f"{a} {b}\n" for a, b in fb.tolist()))
+    return str(d)
+
+
+def test_parse_reference_datasets(snap_files):
     """The two SNAP datasets bundled with the reference parse to their
     documented shapes (Email-Enron header: 36692 nodes / 183831
     undirected edges stored as 367662 directed lines; facebook_combined:
     4039 nodes / 88234 undirected edges, no header)."""
     from bigclam.io import load_graph
 
-    g = load_graph(os.path.join(_REF_DATA, "Email-Enron.txt"))
+    g = load_graph(os.path.join(snap_files, "Email-Enron.txt"))
     assert g.num_nodes == 36692
     assert g.num_edges == 183831  # undirected
     assert len(g.indices) == 2 * 183831
 
-    fb = load_graph(os.path.join(_REF_DATA, "facebook_combined.txt"))
+    fb = load_graph(os.path.join(snap_files, "facebook_combined.txt"))
     assert fb.num_nodes == 4039
     assert fb.num_edges == 88234
 
 
-@_pytest.mark.skipif(
-    not os.path.isdir(_REF_DATA), reason="reference datasets not mounted"
-)
-def test_fit_real_enron_smoke():
+def test_fit_real_enron_smoke(snap_files):
     """Two sweeps on the REAL Email-Enron graph (CPU): LLH finite and
     improving — the reference's own manual verification procedure
      on its own dataset."""
@@ -131,7 +152,7 @@ def test_fit_real_enron_smoke():
     from bigclam.engine.trainer import Trainer
     from bigclam.io import load_graph
 
-    g = load_graph(os.path.join(_REF_DATA, "Email-Enron.txt"))
+    g = load_graph(os.path.join(snap_files, "Email-Enron.txt"))
     cfg = BigClamConfig(k=8, device="cpu", max_sweeps=2, seed=1)
     tr = Trainer(g, cfg, rank=0, world_size=1, device=torch.device("cpu"))
     res = tr.fit(init="random")
@@ -140,10 +161,7 @@ def test_fit_real_enron_smoke():
     assert res.llh_history[-1] > res.llh_history[0]
 
 
-@_pytest.mark.skipif(
-    not os.path.isdir(_REF_DATA), reason="reference datasets not mounted"
-)
-def test_fit_facebook_k25_baseline_config():
+def test_fit_facebook_k25_baseline_config(snap_files):
     """BASELINE.json config #1: facebook_combined K=25 on CPU (gloo ws=1
     plumbing config) — converging fit on the real fixture."""
     import numpy as np
@@ -153,7 +171,7 @@ def test_fit_facebook_k25_baseline_config():
     from bigclam.engine.trainer import Trainer
     from bigclam.io import load_graph
 
-    g = load_graph(os.path.join(_REF_DATA, "facebook_combined.txt"))
+    g = load_graph(os.path.join(snap_files, "facebook_combined.txt"))
     assert g.num_nodes == 4039 and g.num_edges == 88234
     cfg = BigClamConfig(k=25, device="cpu", max_sweeps=4, seed=2)
     tr = Trainer(g, cfg, rank=0, world_size=1, device=torch.device("cpu"))
