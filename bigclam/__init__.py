@@ -17,6 +17,8 @@ __all__ = [
     "load_graph",
     "select_k",
     "extract_communities",
+    "evaluate_covers",
+    "load_cover",
     "__version__",
 ]
 
@@ -38,4 +40,12 @@ def __getattr__(name):  # lazy: keep `import bigclam` light (no torch)
         from .engine.extract import extract_communities
 
         return extract_communities
+    if name == "evaluate_covers":
+        from .engine.evaluate import evaluate_covers
+
+        return evaluate_covers
+    if name == "load_cover":
+        from .io import load_cover
+
+        return load_cover
     raise AttributeError(name)

@@ -5,8 +5,10 @@ SURVEY.md §2.15); this exposes the full hyperparameter set with the
 reference's defaults.
 
   fit        fit a K-community model on an edge list, write communities + ckpt
+             (--truth FILE|planted adds avg best-match F1/Jaccard)
   select-k   model selection over the geometric K grid (v4 semantics)
   extract    re-extract communities from a checkpoint
+  eval       score a detected cover against a ground-truth cover
   bench      one timed sweep loop (see also bench.py at the repo root)
 """
 from __future__ import annotations
@@ -76,7 +78,30 @@ def _cfg_from(args) -> BigClamConfig:
     )
 
 
+PLANTED_SEED = 42  # planted:<...> graphs are the same on every invocation
+
+
 def _load(args):
+    if args.edgelist.startswith("planted:"):
+        # planted:<communities>:<size>:<overlap>[:<p_in>:<bg_edges>] —
+        # overlapping planted communities (io/synthetic.py
+        # planted_overlap); the generator's ground truth is kept for
+        # `--truth planted`
+        from .io import planted_overlap
+
+        parts = args.edgelist.split(":")[1:]
+        if len(parts) not in (3, 5):
+            raise SystemExit(
+                "planted:<communities>:<size>:<overlap>[:<p_in>:<bg_edges>]"
+            )
+        p_in = float(parts[3]) if len(parts) == 5 else 0.5
+        bg = int(parts[4]) if len(parts) == 5 else 0
+        g, truth = planted_overlap(
+            int(parts[0]), int(parts[1]), int(parts[2]), p_in, bg,
+            seed=PLANTED_SEED,
+        )
+        args.planted_truth = truth
+        return g
     if args.edgelist.startswith("rmat:"):
         # rmat:<scale>:<edge_factor> synthetic graph
         _, scale, ef = args.edgelist.split(":")
@@ -103,6 +128,49 @@ def _load(args):
     return load_graph(args.edgelist)
 
 
+def _truth_cover(args, g):
+    """The --truth cover over g's dense ids (None without --truth)."""
+    from .io import Cover, load_cover
+
+    if not getattr(args, "truth", None):
+        return None
+    if args.truth == "planted":
+        members = getattr(args, "planted_truth", None)
+        if members is None:
+            raise SystemExit("--truth planted needs a planted:<...> graph")
+        return Cover.from_raw_members(members, g.raw_ids)
+    return load_cover(args.truth, g.raw_ids)
+
+
+def _cmd_eval(args) -> int:
+    from .engine.evaluate import (
+        evaluate_covers,
+        summary,
+        write_per_community,
+    )
+    from .io import Cover, read_cover_lines
+
+    det = read_cover_lines(args.detected)
+    truth = read_cover_lines(args.truth)
+    if args.graph:
+        raw_ids = _load(argparse.Namespace(edgelist=args.graph)).raw_ids
+    else:  # densify over the union of both files' ids
+        ids = [m for m in det + truth if len(m)]
+        raw_ids = (
+            np.unique(np.concatenate(ids)) if ids
+            else np.empty(0, dtype=np.int64)
+        )
+    res = evaluate_covers(
+        Cover.from_raw_members(det, raw_ids),
+        Cover.from_raw_members(truth, raw_ids),
+        device=args.device,
+    )
+    if args.per_community:
+        write_per_community(args.per_community, res)
+    print(json.dumps(summary(res)))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(
         prog="bigclam",
@@ -123,6 +191,15 @@ def main(argv=None):
         help="resume the fit from a checkpoint directory (any world size)",
     )
 
+    p_fit.add_argument(
+        "--truth",
+        metavar="FILE|planted",
+        default=None,
+        help="ground-truth cover file (one community per line); adds the "
+        "average best-match F1/Jaccard to the result.  'planted' = the "
+        "planted:<...> generator's own truth",
+    )
+
     p_sel = sub.add_parser(
         "select-k", help="model selection over the geometric K grid "
         "(the reference v4 semantics)")
@@ -138,6 +215,18 @@ def main(argv=None):
     p_ext.add_argument("checkpoint_dir")
     p_ext.add_argument("edgelist")
     p_ext.add_argument("--out", required=True)
+
+    p_eval = sub.add_parser(
+        "eval", help="average best-match F1/Jaccard of a detected cover "
+        "against a ground-truth cover")
+    p_eval.add_argument("detected", help="cover file (fit --out format)")
+    p_eval.add_argument("truth", help="cover file (SNAP cmty format)")
+    p_eval.add_argument(
+        "--graph", metavar="EDGELIST", default=None,
+        help="map ids through this graph (ids not in it are dropped); "
+        "default: densify over the union of both files")
+    p_eval.add_argument("--device", default=None, help="cuda|cpu (auto)")
+    p_eval.add_argument("--per-community", metavar="OUT.tsv", default=None)
 
     sub.add_parser(
         "bench",
@@ -167,6 +256,8 @@ def main(argv=None):
         return 0
 
     args = ap.parse_args(argv)
+    if args.cmd == "eval":
+        return _cmd_eval(args)
     rank = comm.init_distributed()
 
     if args.cmd == "extract":
@@ -202,28 +293,46 @@ def main(argv=None):
         from .ckpt.checkpoint import save_shard_checkpoint
 
         save_shard_checkpoint(cfg.checkpoint_dir, tr, res.sweeps, res.llh)
-    if cfg.out:
+    truth = _truth_cover(args, g)
+    scores = {}
+    if cfg.out or truth is not None:
         # sharded K7: per-rank device-side threshold, compacted lists to
-        # rank 0 — no N×K gather
+        # rank 0 — no N×K gather; one extraction serves
+        # both the output file and the ground-truth evaluation
         from .engine.extract import (
             extract_communities_sharded,
             write_membership_pairs,
         )
 
         pairs = extract_communities_sharded(tr)
-        if rank == 0:
+        if rank == 0 and cfg.out:
             write_membership_pairs(cfg.out, pairs[0], pairs[1], g.raw_ids)
+        if rank == 0 and truth is not None:
+            from .engine.evaluate import evaluate_pairs
+
+            ev = evaluate_pairs(
+                pairs, g.num_nodes, cfg.k, truth, device=tr.state.device
+            )
+            scores = {
+                key: ev[key]
+                for key in ("avg_f1", "avg_jaccard", "n_truth", "n_detected")
+            }
+            metrics.log(dict(scores, note="truth_eval",
+                             truth_nodes_dropped=ev["truth_nodes_dropped"]))
     if rank == 0:
         print(
             json.dumps(
-                {
-                    "llh": res.llh,
-                    "sweeps": res.sweeps,
-                    "converged": res.converged,
-                    "n": g.num_nodes,
-                    "edges": g.num_edges,
-                    "k": cfg.k,
-                }
+                dict(
+                    {
+                        "llh": res.llh,
+                        "sweeps": res.sweeps,
+                        "converged": res.converged,
+                        "n": g.num_nodes,
+                        "edges": g.num_edges,
+                        "k": cfg.k,
+                    },
+                    **scores,
+                )
             )
         )
     return 0

@@ -1,5 +1,7 @@
+from .cover import Cover, load_cover, read_cover_lines
 from .edgelist import Graph, build_graph, load_graph, parse_edge_array
 from .synthetic import (
+    planted_overlap,
     planted_partition,
     rmat_edges,
     rmat_graph,
@@ -8,11 +10,15 @@ from .synthetic import (
 )
 
 __all__ = [
+    "Cover",
     "Graph",
     "build_graph",
     "load_graph",
+    "load_cover",
     "parse_edge_array",
+    "planted_overlap",
     "planted_partition",
+    "read_cover_lines",
     "rmat_edges",
     "rmat_graph",
     "rmat_graph_with_edges",

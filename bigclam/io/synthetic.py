@@ -8,6 +8,9 @@ graphs of the same shape (BASELINE.json: "synthetic graphs / random-init F").
   100M-edge 8-GPU config and the com-Amazon-shaped bench graph.
 - :func:`planted_partition`: graphs with known ground-truth communities for
   recovery tests (SURVEY.md §4 "planted-partition graphs").
+- :func:`planted_overlap`: a chain of overlapping planted communities with
+  the ground-truth cover, for the F1/Jaccard recovery evaluation
+  (engine/evaluate.py).
 
 R-MAT has no counterpart in the reference (SURVEY.md §2-B note).
 """
@@ -213,3 +216,41 @@ def planted_partition(
         edges.append(np.stack([s[mask], d[mask]], axis=1))
     all_edges = np.concatenate(edges, axis=0)
     return build_graph(all_edges), labels
+
+
+def planted_overlap(
+    num_communities: int,
+    size: int,
+    overlap: int,
+    p_in: float = 0.5,
+    bg_edges: int = 0,
+    seed: int = 0,
+) -> tuple:
+    """Chain of OVERLAPPING planted communities with known ground truth;
+    returns ``(Graph, truth)``, ``truth`` a list of int64 member arrays.
+
+    Community c spans the node range ``[c*(size-overlap),
+    c*(size-overlap)+size)``, so neighbours in the chain share ``overlap``
+    nodes.  Within a community every pair is an edge with probability
+    ``p_in``; ``bg_edges`` uniform random background pairs are added on
+    top.  The truth is in RAW ids (the generated node numbers): a node
+    that ends up without an edge is absent from the Graph, and mapping
+    the truth through ``Graph.raw_ids`` (``Cover.from_raw_members``)
+    handles that.  Memory is O(size²) per community, so 5000×70 is cheap.
+    """
+    if not 0 <= overlap < size:
+        raise ValueError("need 0 <= overlap < size")
+    rng = np.random.default_rng(seed)
+    stride = size - overlap
+    n = (num_communities - 1) * stride + size
+    iu, ju = np.triu_indices(size, k=1)
+    edges = []
+    truth = []
+    for c in range(num_communities):
+        base = c * stride
+        mask = rng.random(len(iu)) < p_in
+        edges.append(np.stack([base + iu[mask], base + ju[mask]], axis=1))
+        truth.append(np.arange(base, base + size, dtype=np.int64))
+    if bg_edges:
+        edges.append(rng.integers(0, n, size=(int(bg_edges), 2)))
+    return build_graph(np.concatenate(edges, axis=0)), truth

@@ -23,6 +23,8 @@
 //                       grad+Armijo, sparse commit + list rewrite)
 //   K6 k6_seed_init     — device seed-init scatter (scala:60-87)
 //   K7 k7_membership    — device community extraction (Bigclamv2:223-230)
+//   K8 k8_cover_match   — ground-truth best-match F1/Jaccard; lives in
+//                       cover_kernels.hip (integer-only, deterministic)
 //
 // Design notes (measured rationale in profiles/r01_kernel_opt_log.md):
 //  * K1 is BLOCK-per-node: per edge the workgroup does one cooperative dot
@@ -2535,7 +2537,9 @@ __global__ void __launch_bounds__(BLOCK) kaf_support_t(
 //     parallelism.  The atomics make gacc's fp32 summation order
 //     run-dependent (unlike every dense kernel): the sparse path's
 //     documented determinism trade (BIGCLAM_SPARSE=0 restores bitwise
-//     reproducibility);
+//     reproducibility).  K8 (cover_kernels.hip) also uses LDS atomicAdd,
+//     but on INTEGER counters — order-independent, so it is deterministic
+//     and no exception to this note;
 //   * the 16-candidate trial phase runs on an (edge-slot × candidate)
 //     THREAD mapping — no wave-wide reductions;
 //   * one packed 3-value block reduction (gg, fs, ff).

@@ -66,6 +66,12 @@ extern "C" void launch_k7_count(const void*, int, int, int, int, float, int*,
                                 hipStream_t);
 extern "C" void launch_k7_fill(const void*, int, int, int, int, float,
                                const long long*, int*, hipStream_t);
+extern "C" void launch_k8_cover_match(const long long*, const int*,
+                                      const long long*, const int*,
+                                      const int*, int, long long, int,
+                                      long long, int, int, int*, int*,
+                                      hipStream_t);
+extern "C" int k8_max_tile();
 extern "C" void launch_mfma_probe_bf16(const void*, const void*, float*,
                                        hipStream_t);
 extern "C" void launch_mfma_probe_f32(const float*, const float*, float*,
@@ -533,6 +539,44 @@ void extract_fill(torch::Tensor F_local, int64_t k_true, double delta,
                  comms.data_ptr<int>(), current_stream());
 }
 
+// K8: best-match community of cover Y for every community of cover X
+// (exact integer selection; see k8_cover_match in cover_kernels.hip).
+// X is group-major (grp_ptr/grp_nodes), Y node-major (node_ptr/node_comm,
+// ascending per node) with its community sizes in size_y.
+void cover_best_match(torch::Tensor grp_ptr, torch::Tensor grp_nodes,
+                      torch::Tensor node_ptr, torch::Tensor node_comm,
+                      torch::Tensor size_y, int64_t tile,
+                      torch::Tensor best_idx, torch::Tensor best_inter) {
+  CHECK_IN(grp_ptr, torch::kInt64);
+  CHECK_IN(grp_nodes, torch::kInt32);
+  CHECK_IN(node_ptr, torch::kInt64);
+  CHECK_IN(node_comm, torch::kInt32);
+  CHECK_IN(size_y, torch::kInt32);
+  CHECK_IN(best_idx, torch::kInt32);
+  CHECK_IN(best_inter, torch::kInt32);
+  TORCH_CHECK(grp_ptr.dim() == 1 && grp_ptr.size(0) >= 1,
+              "grp_ptr must be [G+1]");
+  TORCH_CHECK(node_ptr.dim() == 1 && node_ptr.size(0) >= 1,
+              "node_ptr must be [N+1]");
+  TORCH_CHECK(tile >= 1 && tile <= k8_max_tile(), "tile must be in [1, ",
+              k8_max_tile(), "], got ", tile);
+  const int64_t G = grp_ptr.size(0) - 1;
+  const int64_t N = node_ptr.size(0) - 1;
+  const int64_t Gy = size_y.size(0);
+  TORCH_CHECK(N < (int64_t(1) << 31), "N must be < 2^31");
+  TORCH_CHECK(G < (int64_t(1) << 31) && Gy < (int64_t(1) << 31),
+              "community counts must be < 2^31");
+  TORCH_CHECK(best_idx.size(0) == G && best_inter.size(0) == G,
+              "best_idx/best_inter must be [G]");
+  launch_k8_cover_match(i64p(grp_ptr), grp_nodes.data_ptr<int>(),
+                        i64p(node_ptr), node_comm.data_ptr<int>(),
+                        size_y.data_ptr<int>(), (int)G,
+                        (long long)grp_nodes.size(0), (int)N,
+                        (long long)node_comm.size(0), (int)Gy, (int)tile,
+                        best_idx.data_ptr<int>(), best_inter.data_ptr<int>(),
+                        current_stream());
+}
+
 void conductance(torch::Tensor indptr, torch::Tensor indices,
                  torch::Tensor cond, double total_degree) {
   CHECK_IN(indptr, torch::kInt64);
@@ -579,6 +623,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K7 pass 1: per-row membership counts (threshold/argmax-fallback)");
   m.def("extract_fill", &extract_fill,
         "K7 pass 2: write ascending community ids at per-row offsets");
+  m.def("cover_best_match", &cover_best_match,
+        "K8: exact best-match (F1/Jaccard argmax) of cover Y per community "
+        "of cover X, tiled LDS intersection histogram");
+  m.attr("COVER_MAX_TILE") = k8_max_tile();
   m.def("mfma_probe", &mfma_probe,
         "MFMA C/D layout probe: one 16x16 D = A @ Bc^T tile");
 }

@@ -2,6 +2,7 @@
 
 ``reference``: vectorized torch implementations (CPU path + numerics
 reference).  ``hip``: hand-written CDNA4 HIP kernels (GPU path; requires the
-in-tree ``bigclam._C`` extension built for gfx950).
+in-tree ``bigclam._C`` extension built for gfx950).  ``cover_cpu``: the
+vectorised CPU best-match between two covers (CPU path + oracle of K8).
 """
 from . import reference  # noqa: F401

@@ -349,3 +349,36 @@ def full_llh(
     llh = torch.empty(n_local, device=F.device, dtype=torch.float64)
     ext.llh_only(F, indptr, indices, sumF, order, llh, cfg.min_p, cfg.max_p)
     return llh.sum()
+
+
+def cover_max_tile() -> int:
+    """Compiled maximum of K8's LDS tile (counters per block)."""
+    return int(ensure_loaded().COVER_MAX_TILE)
+
+
+def cover_best_match(
+    grp_ptr: torch.Tensor,
+    grp_nodes: torch.Tensor,
+    node_ptr: torch.Tensor,
+    node_comm: torch.Tensor,
+    size_y: torch.Tensor,
+    tile: int = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """K8: for every community of cover X (group-major ``grp_ptr``/
+    ``grp_nodes``) the best-matching community of cover Y (node-major
+    ``node_ptr``/``node_comm`` ascending per node, sizes ``size_y``) under
+    the exact F1/Jaccard argmax (ops/cover_cpu.py is the same contract on
+    CPU).  Returns ``(best_idx int32 [G], best_inter int32 [G])`` on
+    device; ``tile`` defaults to the compiled maximum (16384 counters)."""
+    ext = ensure_loaded()
+    if tile is None:
+        tile = int(ext.COVER_MAX_TILE)
+    g = max(int(grp_ptr.shape[0]) - 1, 0)
+    dev = grp_ptr.device
+    best_idx = torch.empty(g, device=dev, dtype=torch.int32)
+    best_inter = torch.empty(g, device=dev, dtype=torch.int32)
+    ext.cover_best_match(
+        grp_ptr, grp_nodes, node_ptr, node_comm, size_y, int(tile),
+        best_idx, best_inter,
+    )
+    return best_idx, best_inter

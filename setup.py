@@ -28,6 +28,7 @@ setup(
             sources=[
                 "bigclam/kernels/bindings.cpp",
                 "bigclam/kernels/bigclam_kernels.hip",
+                "bigclam/kernels/cover_kernels.hip",
             ],
             extra_compile_args={
                 "cxx": ["-O3"],
