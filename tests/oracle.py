@@ -195,3 +195,221 @@ def armijo_margin_f64(graph, F, grad_u, u, s, cfg):
 
     fu2 = np.clip(Fd[u] + s * gu, cfg.min_f, cfg.max_f)
     return llh_u(fu2) - llh_u(Fd[u]) - cfg.alpha * s * (gu @ gu)
+
+
+# ---------------------------------------------------------------------------
+# Vectorised fp64 contract oracle (docs/kernels.md, "Numerics contract").
+#
+# Same math as the loop oracle above, organised as per-node matrix products
+# ((deg x K) @ (K x n_ladder)) so that N ~ 650 nodes at K up to 16392 is
+# cheap.  It works in a shard's LOCAL index space (rows [0, n_local) owned,
+# halo rows after them), takes the STORED F values upcast exactly
+# (bf16 -> fp64 is exact) and the fp32 sumF the kernel is given, and returns
+# the fp64 result together with the condition scales the error bounds hang
+# on.
+#
+# Tolerances are C * EPS32 * scale.  The constants were MEASURED on the CPU
+# against the fp32 torch reference (bigclam/ops/reference.py, plus the fp32
+# trial evaluation tests/contract_fixtures.ref_trials) over every fixture in
+# tests/contract_fixtures.all_cases(), never against the HIP kernels:
+# C = 8 x (largest normalised error of the reference), rounded up to a power
+# of two.  The 8x covers the kernels' different reduction order (strided
+# partials + wave butterfly + LDS round) and __expf/log1pf being a few ulp
+# instead of one.  tests/test_oracle.py::test_reference_meets_contract
+# re-measures the maxima and asserts they stay under C/8.
+#
+#   measured maxima of |ref - fp64| / (eps32 * scale) over all 52 fixtures
+#   (largest over the two hosts measured; torch's CPU sum order and
+#   exp/log1p differ with the vector width, which moves the margin figure:
+#   106.5 on one x86 host, 127.0 on another):
+#     grad    45.1  (small ladder, dense, bf16 K=9)     -> 8x =  361 -> 512
+#     llh      9.87 (small ladder, dense, bf16 K=9)     -> 8x =   79 -> 128
+#     margin 127.0  (small ladder, dense, bf16 K=8185)  -> 8x = 1016 -> 1024
+# The maxima are well above 1 because the scales model the error of x but
+# not the half-ulp rounding of p = exp(-x) itself, which 1/(1-p) and
+# log(1-p) amplify by p/(1-p) ~ 1/x on edges with small x (leaf rows with
+# scale 0.01; candidate rows clamped to nearly zero).
+EPS32 = 2.0 ** -23
+MEASURED_MAX = {"grad": 45.1, "llh": 9.87, "margin": 127.05}
+C_GRAD = 512.0
+C_LLH = 128.0
+C_MARGIN = 1024.0
+# bf16 MFMA phase B rounds the clamped candidate rows to bf16 (relative
+# error 2^-9 per element, RNE): derived, not measured.
+BF16_CAND_EPS = 2.0 ** -9
+# share of nodes whose pick may differ from the exact pick (the caps the
+# project already used: 2% fp32 paths, 5% bf16 paths; < 100 nodes: 2 nodes)
+PICK_CAP = {"fp32": 0.02, "bf16": 0.05}
+
+
+def _f32(v):
+    """A config scalar as the kernels receive it: rounded to fp32.  (With
+    max_p = 0.9999 the rounding moves log(1 - p) by 3e-4 relative.)"""
+    return float(np.float32(v))
+
+
+def _cfg_ladder32(cfg):
+    """The ladder as the kernels see it: fp32 values, upcast."""
+    return np.asarray(cfg.ladder(), dtype=np.float32).astype(np.float64)
+
+
+def vec_grad_llh(F, sumF, indptr, indices, cfg, n_local=None):
+    """fp64 gradient/LLH of every owned node plus condition scales.
+
+    Returns dict(grad [n,K], llh [n], A [n,K], L [n], n_min_p, n_max_p):
+      X_e  = sum_k |fu_k||fv_k|
+      dw_e = p_e/(1-p_e)^2 where the p-clamp is inactive, else 0
+      A[u,k] = sum_e (w_e + dw_e X_e)|fv_k| + |sumF_k| + |fu_k|
+      L[u]   = sum_e (|log(1-p_e)| + (1 + p_e/(1-p_e)) X_e)
+               + sum_k |fu_k|(|sumF_k| + |fu_k|)
+    n_min_p / n_max_p count the edges on which either p-clamp is active.
+    """
+    F = np.asarray(F, dtype=np.float64)
+    sumF = np.asarray(sumF, dtype=np.float64)
+    n = len(indptr) - 1 if n_local is None else n_local
+    K = F.shape[1]
+    grad = np.empty((n, K))
+    A = np.empty((n, K))
+    llh = np.empty(n)
+    L = np.empty(n)
+    n_min_p = n_max_p = 0
+    aS = np.abs(sumF)
+    for u in range(n):
+        fu = F[u]
+        Fv = F[indices[indptr[u] : indptr[u + 1]]]
+        x = Fv @ fu
+        X = np.abs(Fv) @ np.abs(fu)
+        praw = np.exp(-x)
+        p = np.clip(praw, _f32(cfg.min_p), _f32(cfg.max_p))
+        free = (praw > _f32(cfg.min_p)) & (praw < _f32(cfg.max_p))
+        n_min_p += int((praw <= _f32(cfg.min_p)).sum())
+        n_max_p += int((praw >= _f32(cfg.max_p)).sum())
+        w = 1.0 / (1.0 - p)
+        dw = np.where(free, p / (1.0 - p) ** 2, 0.0)
+        grad[u] = w @ Fv - sumF + fu
+        A[u] = (w + dw * X) @ np.abs(Fv) + aS + np.abs(fu)
+        llh[u] = np.sum(np.log1p(-p) + x) - fu @ sumF + fu @ fu
+        L[u] = np.sum(np.abs(np.log1p(-p)) + (1.0 + p / (1.0 - p)) * X) + np.abs(
+            fu
+        ) @ (aS + np.abs(fu))
+    return dict(grad=grad, llh=llh, A=A, L=L, n_min_p=n_min_p, n_max_p=n_max_p)
+
+
+def vec_margins(F, sumF, indptr, indices, cfg, grad, llh, n_local=None):
+    """Armijo margins of every ladder rung for every owned node, given a
+    gradient row and base LLH per node (the tests pass the implementation's
+    OWN grad/llh upcast, so phase B is judged separately from phase A).
+
+    Returns dict(m [n,J], M [n,J], B [n,J], trial [n,J], pick [n],
+    n_max_f): m = trial64_j - llh_u - alpha s_j |g|^2; M its scale (built
+    like L on the candidate row, node term bounded by
+    sum|fc_k|(|sumF_k| + |fu_k|), plus alpha s_j |g|^2); B the bf16
+    candidate-rounding scale sum_e (1 + p/(1-p)) X'_e; pick the exact pick
+    (first j with m >= 0, else -1); n_max_f the number of candidate
+    entries on the upper F clamp.
+    """
+    F = np.asarray(F, dtype=np.float64)
+    sumF = np.asarray(sumF, dtype=np.float64)
+    grad = np.asarray(grad, dtype=np.float64)
+    llh = np.asarray(llh, dtype=np.float64)
+    n = len(indptr) - 1 if n_local is None else n_local
+    s = _cfg_ladder32(cfg)
+    J = len(s)
+    m = np.empty((n, J))
+    M = np.empty((n, J))
+    B = np.empty((n, J))
+    trial = np.empty((n, J))
+    n_max_f = 0
+    aS = np.abs(sumF)
+    for u in range(n):
+        fu = F[u]
+        g = grad[u]
+        Fv = F[indices[indptr[u] : indptr[u + 1]]]
+        raw = fu[:, None] + g[:, None] * s[None, :]
+        n_max_f += int((raw >= _f32(cfg.max_f)).sum())
+        C = np.clip(raw, _f32(cfg.min_f), _f32(cfg.max_f))  # [K, J]
+        x = Fv @ C  # [deg, J]
+        X = np.abs(Fv) @ np.abs(C)
+        p = np.clip(np.exp(-x), _f32(cfg.min_p), _f32(cfg.max_p))
+        amp = (1.0 + p / (1.0 - p)) * X
+        gg = float(g @ g)
+        arm = cfg.alpha * s * gg
+        trial[u] = np.sum(np.log1p(-p) + x, axis=0) - (sumF - fu) @ C
+        m[u] = trial[u] - llh[u] - arm
+        B[u] = amp.sum(axis=0)
+        M[u] = (
+            np.sum(np.abs(np.log1p(-p)), axis=0)
+            + B[u]
+            + (aS + np.abs(fu)) @ np.abs(C)
+            + np.abs(arm)
+        )
+    ok = m >= 0
+    pick = np.where(ok.any(axis=1), ok.argmax(axis=1), -1)
+    return dict(m=m, M=M, B=B, trial=trial, pick=pick, n_max_f=n_max_f)
+
+
+def vec_commit(F_local, grad, steps, cfg):
+    """fp64 projected commit: clamp(fu + s g) where s > 0, else unchanged."""
+    F = np.asarray(F_local, dtype=np.float64)
+    g = np.asarray(grad, dtype=np.float64)
+    s = np.asarray(steps, dtype=np.float64)[:, None]
+    return np.where(s > 0, np.clip(F + s * g, _f32(cfg.min_f), _f32(cfg.max_f)), F)
+
+
+def steps_to_rungs(best, cfg):
+    """Map an implementation's best-step values to ladder rung indices
+    (-1 = no step).  A value that is neither 0 nor an fp32 ladder entry is
+    a contract violation in itself."""
+    lad = np.asarray(cfg.ladder(), dtype=np.float32)
+    best = np.asarray(best, dtype=np.float32)
+    rung = np.full(best.shape, -2, dtype=np.int64)
+    rung[best == 0] = -1
+    for j in range(len(lad) - 1, -1, -1):  # descending ladder: all distinct
+        rung[best == lad[j]] = j
+    assert (rung > -2).all(), "best step is not a ladder value: %r" % (
+        best[rung == -2][:5],
+    )
+    return rung
+
+
+def grad_violations(grad, o, c_grad=None):
+    """Entries of an implementation's grad outside C*eps32*A of grad64."""
+    c = C_GRAD if c_grad is None else c_grad
+    err = np.abs(np.asarray(grad, dtype=np.float64) - o["grad"])
+    return np.argwhere(err > c * EPS32 * o["A"])
+
+
+def llh_violations(llh, o, c_llh=None):
+    c = C_LLH if c_llh is None else c_llh
+    err = np.abs(np.asarray(llh, dtype=np.float64) - o["llh"])
+    return np.flatnonzero(err > c * EPS32 * o["L"])
+
+
+def pick_violations(rung, mo, bf16_candidates=False, c_margin=None):
+    """Nodes whose pick breaks the acceptance rule (EVERY node is judged):
+    no earlier rung clearly acceptable (m <= T for all j < j*), the chosen
+    rung not clearly rejected (m[j*] >= -T); for "no step" every rung has
+    m <= T.  T = C_MARGIN eps32 M (+ 2^-9 B where the implementation rounds
+    candidate rows to bf16).  Returns (bad node ids, nodes differing from
+    the exact pick)."""
+    c = C_MARGIN if c_margin is None else c_margin
+    T = c * EPS32 * mo["M"]
+    if bf16_candidates:
+        T = T + BF16_CAND_EPS * mo["B"]
+    m = mo["m"]
+    n, J = m.shape
+    jj = np.arange(J)[None, :]
+    stop = np.where(rung < 0, J, rung)[:, None]
+    earlier_clear = ((m > T) & (jj < stop)).any(axis=1)
+    rows = np.flatnonzero(rung >= 0)
+    rejected = np.zeros(n, dtype=bool)
+    rejected[rows] = m[rows, rung[rows]] < -T[rows, rung[rows]]
+    bad = np.flatnonzero(earlier_clear | rejected)
+    differ = np.flatnonzero(rung != mo["pick"])
+    return bad, differ
+
+
+def pick_cap_ok(n_differ, n_nodes, dtype):
+    if n_nodes < 100:
+        return n_differ <= 2
+    return n_differ <= PICK_CAP[dtype] * n_nodes
