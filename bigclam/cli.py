@@ -5,8 +5,10 @@ SURVEY.md §2.15); this exposes the full hyperparameter set with the
 reference's defaults.
 
   fit        fit a K-community model on an edge list, write communities + ckpt
-             (--truth FILE|planted adds avg best-match F1/Jaccard)
-  select-k   model selection over the geometric K grid (v4 semantics)
+             (--truth FILE|planted adds avg best-match F1/Jaccard;
+             --holdout FRAC adds held-out likelihood + link-prediction AUC)
+  select-k   model selection over the geometric K grid (v4 semantics;
+             --holdout FRAC: the K with the highest held-out likelihood)
   extract    re-extract communities from a checkpoint
   eval       score a detected cover against a ground-truth cover
   bench      one timed sweep loop (see also bench.py at the repo root)
@@ -53,6 +55,18 @@ def _add_common(p: argparse.ArgumentParser):
     p.add_argument("--out", default=None)
     p.add_argument("--metrics", default=None, help="JSONL metrics path")
     p.add_argument("--quiet", action="store_true")
+    p.add_argument(
+        "--holdout", metavar="FRAC", type=float, default=None,
+        help="hold out this fraction of the edges (and as many sampled "
+        "non-edges), fit on the rest and report held-out likelihood and "
+        "link-prediction AUC; with select-k: choose K by held-out "
+        "likelihood",
+    )
+    p.add_argument("--holdout-seed", type=int, default=0)
+    p.add_argument(
+        "--holdout-neg-ratio", type=float, default=1.0,
+        help="sampled non-edges per held-out edge",
+    )
 
 
 def _cfg_from(args) -> BigClamConfig:
@@ -209,6 +223,11 @@ def main(argv=None):
     p_sel.add_argument("--k-max", dest="k_max", type=int, default=9000)
     p_sel.add_argument("--k-div", dest="k_div", type=int, default=100)
     p_sel.add_argument("--k-tol", dest="k_tol", type=float, default=1e-3)
+    p_sel.add_argument(
+        "--k-patience", dest="k_patience", type=int, default=2,
+        help="with --holdout: stop after this many consecutive grid points "
+        "without a better held-out likelihood (0 = whole grid)",
+    )
 
     p_ext = sub.add_parser(
         "extract", help="re-extract communities from a checkpoint")
@@ -258,6 +277,12 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.cmd == "eval":
         return _cmd_eval(args)
+    holdout = getattr(args, "holdout", None)
+    if holdout is not None and getattr(args, "resume", None):
+        raise SystemExit(
+            "--holdout cannot be combined with --resume: the checkpoint "
+            "does not record the edge split it was fitted on"
+        )
     rank = comm.init_distributed()
 
     if args.cmd == "extract":
@@ -275,12 +300,29 @@ def main(argv=None):
     metrics = MetricsLogger(args.metrics, rank=rank, quiet=args.quiet)
 
     if args.cmd == "select-k":
-        out = select_k(g, cfg, metrics=metrics, init=args.init)
+        out = select_k(
+            g, cfg, metrics=metrics, init=args.init, holdout=holdout,
+            holdout_seed=args.holdout_seed,
+            neg_ratio=args.holdout_neg_ratio, patience=args.k_patience,
+        )
         if rank == 0:
             print(json.dumps(out))
         return 0
 
-    tr = Trainer(g, cfg, metrics=metrics)
+    split = None
+    if holdout is not None:
+        # fit on the train graph; it keeps g's node space, so --out and
+        # --truth below work unchanged
+        import time
+
+        from .io.holdout import split_edges
+
+        t0 = time.perf_counter()
+        split = split_edges(
+            g, holdout, args.holdout_seed, args.holdout_neg_ratio
+        )
+        split_s = time.perf_counter() - t0
+    tr = Trainer(g if split is None else split.train, cfg, metrics=metrics)
     if getattr(args, "resume", None):
         from .ckpt.checkpoint import resume as ckpt_resume
 
@@ -319,6 +361,17 @@ def main(argv=None):
             }
             metrics.log(dict(scores, note="truth_eval",
                              truth_nodes_dropped=ev["truth_nodes_dropped"]))
+    if split is not None:
+        from .engine.holdout import heldout_metrics
+
+        hm = heldout_metrics(tr, split)  # collective; dict on rank 0
+        if rank == 0:
+            metrics.log(dict(hm, note="heldout_eval", split_s=split_s,
+                             train_edges=split.train.num_edges))
+            scores.update(
+                {key: hm[key] for key in ("heldout_llh", "heldout_auc",
+                                          "heldout_pos", "heldout_neg")}
+            )
     if rank == 0:
         print(
             json.dumps(

@@ -72,6 +72,9 @@ extern "C" void launch_k8_cover_match(const long long*, const int*,
                                       long long, int, int, int*, int*,
                                       hipStream_t);
 extern "C" int k8_max_tile();
+extern "C" void launch_k9_pair_dot(const void*, const void*, int, const int*,
+                                   const int*, float*, long long, int, int,
+                                   int, hipStream_t);
 extern "C" void launch_mfma_probe_bf16(const void*, const void*, float*,
                                        hipStream_t);
 extern "C" void launch_mfma_probe_f32(const float*, const float*, float*,
@@ -577,6 +580,62 @@ void cover_best_match(torch::Tensor grp_ptr, torch::Tensor grp_nodes,
                         current_stream());
 }
 
+// K9: x[i] = F[pu[i]] . F[pv[i]] over the row space [F_own ; F_extra]
+// (index < n_own reads F_own, otherwise F_extra[index - n_own]; see
+// k9_pair_dot_t in pair_kernels.hip).  The index range is verified here,
+// once per call, from the min/max of the index tensors — the kernel itself
+// carries no per-element check that could fail.
+void pair_dot(torch::Tensor F_own, torch::Tensor F_extra, torch::Tensor pu,
+              torch::Tensor pv, torch::Tensor x) {
+  CHECK_IN(pu, torch::kInt32);
+  CHECK_IN(pv, torch::kInt32);
+  CHECK_IN(x, torch::kFloat32);
+  TORCH_CHECK(F_own.is_cuda(), "F_own must be on GPU");
+  TORCH_CHECK(F_extra.is_cuda(), "F_extra must be on GPU");
+  TORCH_CHECK(F_own.scalar_type() == torch::kFloat32 ||
+                  F_own.scalar_type() == torch::kBFloat16,
+              "F_own has wrong dtype (fp32 or bf16)");
+  TORCH_CHECK(F_extra.scalar_type() == F_own.scalar_type(),
+              "F_extra has wrong dtype (must match F_own)");
+  TORCH_CHECK(F_own.is_contiguous(), "F_own must be contiguous");
+  TORCH_CHECK(F_extra.is_contiguous(), "F_extra must be contiguous");
+  TORCH_CHECK(F_own.dim() == 2 && F_extra.dim() == 2,
+              "F_own/F_extra must be [rows, kp]");
+  const auto dev = F_own.device();
+  TORCH_CHECK(F_extra.device() == dev && pu.device() == dev &&
+                  pv.device() == dev && x.device() == dev,
+              "all tensors must be on the same device");
+  const int64_t kp = F_own.size(1);
+  TORCH_CHECK(F_extra.size(1) == kp, "F_own and F_extra differ in kp (",
+              kp, " vs ", F_extra.size(1), ")");
+  const bool bf16 = is_bf16(F_own);
+  TORCH_CHECK(kp >= 1 && kp % (bf16 ? 8 : 4) == 0,
+              "kp must be padded to a multiple of ", bf16 ? 8 : 4);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(F_own.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(F_extra.data_ptr()) % 16 == 0,
+              "F_own/F_extra must be 16-byte aligned");
+  TORCH_CHECK(pu.dim() == 1 && pv.dim() == 1 && pu.size(0) == pv.size(0),
+              "pu and pv must be 1-D of the same length");
+  const int64_t P = pu.size(0);
+  TORCH_CHECK(x.dim() == 1 && x.size(0) == P, "x must be [P]");
+  const int64_t n_own = F_own.size(0);
+  const int64_t n_extra = F_extra.size(0);
+  TORCH_CHECK(n_own + n_extra < (int64_t(1) << 31),
+              "row count must be < 2^31");
+  if (P == 0) return;
+  const int64_t lo =
+      std::min(pu.min().item<int64_t>(), pv.min().item<int64_t>());
+  const int64_t hi =
+      std::max(pu.max().item<int64_t>(), pv.max().item<int64_t>());
+  TORCH_CHECK(lo >= 0 && hi < n_own + n_extra,
+              "pair index out of range: [", lo, ", ", hi, "] vs ",
+              n_own + n_extra, " rows");
+  launch_k9_pair_dot(F_own.data_ptr(), F_extra.data_ptr(), bf16 ? 1 : 0,
+                     pu.data_ptr<int>(), pv.data_ptr<int>(),
+                     x.data_ptr<float>(), (long long)P, (int)n_own,
+                     (int)n_extra, (int)kp, current_stream());
+}
+
 void conductance(torch::Tensor indptr, torch::Tensor indices,
                  torch::Tensor cond, double total_degree) {
   CHECK_IN(indptr, torch::kInt64);
@@ -627,6 +686,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K8: exact best-match (F1/Jaccard argmax) of cover Y per community "
         "of cover X, tiled LDS intersection histogram");
   m.attr("COVER_MAX_TILE") = k8_max_tile();
+  m.def("pair_dot", &pair_dot,
+        "K9: F row dot products for arbitrary node pairs over the row space "
+        "[F_own ; F_extra], one wave per pair, deterministic");
   m.def("mfma_probe", &mfma_probe,
         "MFMA C/D layout probe: one 16x16 D = A @ Bc^T tile");
 }

@@ -382,3 +382,21 @@ def cover_best_match(
         best_idx, best_inter,
     )
     return best_idx, best_inter
+
+
+def pair_dot(
+    F_own: torch.Tensor,
+    F_extra: torch.Tensor,
+    pu: torch.Tensor,
+    pv: torch.Tensor,
+) -> torch.Tensor:
+    """K9: ``x[i] = F[pu[i]] · F[pv[i]]`` (fp32) over the row space
+    ``[F_own ; F_extra]`` — an index below ``F_own.shape[0]`` reads
+    ``F_own``, any other reads ``F_extra[idx - n_own]``; the two buffers
+    stay separate.  ``pu``/``pv`` are int32 on the device of F.  Bitwise
+    reproducible and independent of the other pairs in the call
+    (ops/reference.py ``pair_dot`` is the same contract in torch)."""
+    ext = ensure_loaded()
+    x = torch.empty(pu.shape[0], device=F_own.device, dtype=torch.float32)
+    ext.pair_dot(F_own, F_extra, pu, pv, x)
+    return x

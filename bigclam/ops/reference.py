@@ -166,3 +166,55 @@ def full_llh(
         acc = acc + (torch.log1p(-p).double() + x.double()).sum()
     node = (-(Fl @ sf) + (Fl * Fl).sum(-1)).double().sum()
     return acc + node
+
+
+def _pair_rows(F_own: torch.Tensor, F_extra: torch.Tensor,
+               idx: torch.Tensor) -> torch.Tensor:
+    """fp32 rows ``idx`` of the row space [F_own ; F_extra]."""
+    n_own = F_own.shape[0]
+    if F_extra.shape[0] == 0:
+        return F_own.index_select(0, idx).float()
+    own = idx < n_own
+    rows = torch.empty(
+        idx.shape[0], F_own.shape[1], device=F_own.device,
+        dtype=torch.float32,
+    )
+    rows[own] = F_own.index_select(0, idx[own]).float()
+    rows[~own] = F_extra.index_select(0, idx[~own] - n_own).float()
+    return rows
+
+
+def pair_dot(
+    F_own: torch.Tensor,
+    F_extra: torch.Tensor,
+    pu: torch.Tensor,
+    pv: torch.Tensor,
+    chunk: int = None,
+) -> torch.Tensor:
+    """K9 reference: ``x[i] = F[pu[i]] · F[pv[i]]`` (fp32) over the row
+    space ``[F_own ; F_extra]``: an index below ``F_own.shape[0]`` reads
+    ``F_own``, any other reads ``F_extra[idx - n_own]``.  Gather, multiply,
+    ``sum(-1)``, in pair chunks of bounded size (about 2^26 gathered
+    elements per operand unless ``chunk`` says otherwise)."""
+    kp = F_own.shape[1]
+    n_rows = F_own.shape[0] + F_extra.shape[0]
+    p = pu.shape[0]
+    x = torch.empty(p, device=F_own.device, dtype=torch.float32)
+    if p == 0:
+        return x
+    pu = pu.long()
+    pv = pv.long()
+    lo = int(torch.minimum(pu.min(), pv.min()))
+    hi = int(torch.maximum(pu.max(), pv.max()))
+    if lo < 0 or hi >= n_rows:
+        raise IndexError(
+            f"pair index out of range: [{lo}, {hi}] vs {n_rows} rows"
+        )
+    if chunk is None:
+        chunk = max(1, (1 << 26) // max(kp, 1))
+    for i0 in range(0, p, chunk):
+        i1 = min(i0 + chunk, p)
+        a = _pair_rows(F_own, F_extra, pu[i0:i1])
+        b = _pair_rows(F_own, F_extra, pv[i0:i1])
+        x[i0:i1] = (a * b).sum(-1)
+    return x

@@ -29,6 +29,7 @@ setup(
                 "bigclam/kernels/bindings.cpp",
                 "bigclam/kernels/bigclam_kernels.hip",
                 "bigclam/kernels/cover_kernels.hip",
+                "bigclam/kernels/pair_kernels.hip",
             ],
             extra_compile_args={
                 "cxx": ["-O3"],
