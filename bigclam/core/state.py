@@ -140,6 +140,7 @@ class ShardState:
         self._dirty: Optional[torch.Tensor] = None  # uint8 [n_rows]
         self._kaf_valid = False  # persistent support lists match F
         self._side_stream = None  # hub-remainder overlap (sparse path)
+        self._class_edges = None  # routing-class boundaries (device, u8)
         # per-edge source row (torch reference path); built lazily on CPU
         self._edge_src: Optional[torch.Tensor] = None
 
@@ -412,6 +413,25 @@ class ShardState:
         return max(0, min(self.kp // 4, lds_cap) & ~7)
 
     @property
+    def sparse_wcap(self) -> int:
+        """Per-wave slot cap: routed nodes whose bound fits it run the
+        one-wave-per-node kernel (KFW), the rest of the routed nodes the
+        block kernel (KFS).  0 disables KFW.  BIGCLAM_SPARSE_WCAP
+        overrides the default; the value is clamped to ``sparse_cap`` and
+        to what fits a 64 KB wave workgroup (the launcher's own size
+        formula: bitmap + u16 prefix per bitmap word + edge table, plus
+        16|20 bytes per slot)."""
+        if not self.use_hip:
+            return 0
+        env = os.environ.get("BIGCLAM_SPARSE_WCAP")
+        w = int(env) if env is not None else 256
+        lds = _hip_ops().ensure_loaded().sparse_wave_lds_bytes
+        bf = self.storage_dtype == torch.bfloat16
+        fixed = lds(bf, self.kp, 0)
+        per = lds(bf, self.kp, 1) - fixed
+        return max(0, min(w, self.sparse_cap, (65536 - fixed) // per))
+
+    @property
     def sparse_allowed(self) -> bool:
         """Active-column sweep (docs/sparse_sweep_design.md): exact
         per-node routing by active-set bound; pays off once F sparsifies
@@ -454,9 +474,11 @@ class ShardState:
     def grad_ls_auto(self, halo_work):
         """Per-sweep adaptive dispatch: route nodes whose active-set bound
         (own support + sum of neighbor supports, exact upper bound on
-        |S_u|) fits under ``sparse_cap`` to the fused sparse kernel
-        (KFS), the rest to the dense path (fused kernel, or chunked
-        K1 + K2 subsets above its caps).  Returns
+        |S_u|) fits under ``sparse_cap`` to the fused sparse kernels
+        (one wave per node, KFW, when the bound also fits
+        ``sparse_wcap``; one block per node, KFS, otherwise), the rest to
+        the dense path (fused kernel, or chunked K1 + K2 subsets above
+        its caps).  Returns
         (grad, llh_nodes, best, sparse_pack|None)."""
         if not self.sparse_allowed:
             self._last_nnz = None
@@ -494,7 +516,7 @@ class ShardState:
         dev = self.device
         n_rows = self.F.shape[0]
         cap = self.sparse_cap
-        # Single host sync per sweep (the boolean order split below);
+        # Single host sync per sweep (the routing-class sizes below);
         # pools use a fixed per-row stride of `cap` so their sizes are
         # shape-derived, not data-dependent.
         if self._sp_soffset is None or self._sp_cap != cap:
@@ -567,10 +589,26 @@ class ShardState:
         bound, cs = self.sparse_bounds(
             scount, self.indptr, self._indices64, self.n_local
         )
-        is_sparse = bound <= cap
-        om = is_sparse[self._order64]
-        order_s = self.order[om].contiguous()  # <- the one host sync
-        n_s = int(order_s.numel())
+        # three classes by the exact bound: 0 = block kernel (wcap < bound
+        # <= cap), 1 = wave kernel (bound <= wcap), 2 = dense remainder.
+        # A stable sort of the class key over the degree-descending launch
+        # order keeps every class degree-descending and lays the routed
+        # order out as [block | wave]; the class sizes are the sweep's one
+        # host sync.
+        wcap = self.sparse_wcap
+        key = (bound > cap).to(torch.uint8) * 2
+        if wcap > 0:
+            key += (bound <= wcap).to(torch.uint8)
+        skey, perm = torch.sort(key[self._order64], stable=True)
+        if self._class_edges is None:
+            self._class_edges = torch.tensor(
+                [1, 2], device=dev, dtype=torch.uint8
+            )
+        n_blk, n_s = torch.searchsorted(
+            skey, self._class_edges
+        ).tolist()  # <- the one host sync
+        by_class = self.order[perm]
+        order_s = by_class[:n_s]
         # engage only when a real fraction of nodes routes: at low K /
         # moderate density the bound exceeds cap for most nodes and the
         # routing overhead loses (Enron-shaped K=500: 16% routed, sparse
@@ -578,7 +616,7 @@ class ShardState:
         if n_s < max(64, self.n_local // 4):
             g, l, b = self.fused_grad_ls_overlap(None)
             return g, l, b, None
-        order_d = self.order[~om].contiguous()
+        order_d = by_class[n_s:]
         goffset = torch.arange(n_s, device=dev, dtype=torch.int64) * cap
         n, kp = self.n_local, self.kp
         grad = torch.empty(n, kp, device=dev, dtype=torch.float32)
@@ -622,7 +660,9 @@ class ShardState:
             soffset, sidx, sval, scount, cs, goffset,
             self.n_local * cap, cap, llh, best, self.cfg,
             state_pools=(self._sp_gidx, self._sp_gval),
+            n_block=n_blk, wcap=wcap,
         )
+        pack["n_block"] = n_blk  # order[:n_block] block class, rest wave
         if n_d:
             torch.cuda.current_stream(dev).wait_stream(self._side_stream)
         pack["best"] = best

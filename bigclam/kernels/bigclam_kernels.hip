@@ -2531,8 +2531,9 @@ __global__ void __launch_bounds__(BLOCK) kaf_support_t(
 //     LDS bitmap (phase 1 ORs bits while staging), so the accumulator
 //     gacc is COMPACT (cap slots, not K): no O(K) LDS residency, no
 //     O(K) zeroing, and staged entries transform to slot positions once
-//     (binary search) — after that every phase runs on LDS positions
-//     with zero global gathers;
+//     (rank = per-word prefix + popcount of the word's lower bits, two
+//     LDS reads) — after that every phase runs on LDS positions with
+//     zero global gathers;
 //   * WAVE-per-edge dot + scatter via LDS atomicAdd — barrier-free edge
 //     parallelism.  The atomics make gacc's fp32 summation order
 //     run-dependent (unlike every dense kernel): the sparse path's
@@ -2543,8 +2544,8 @@ __global__ void __launch_bounds__(BLOCK) kaf_support_t(
 //   * the 16-candidate trial phase runs on an (edge-slot × candidate)
 //     THREAD mapping — no wave-wide reductions;
 //   * one packed 3-value block reduction (gg, fs, ff).
-// LDS = bitmap K/32 + cap*(16|20) bytes: 21 KB at the headline K=5000
-// bf16 (7 blocks/CU), ~78 KB at K=25000 with the occupancy-aware cap.
+// LDS = bitmap K/32 words (+ a u16 prefix per word) + cap*(16|20) bytes:
+// 21 KB at the headline K=5000 bf16 (7 blocks/CU), ~78 KB at K=25000 with the occupancy-aware cap.
 
 template <bool BF16>
 __device__ __forceinline__ float vget(unsigned short v);
@@ -2588,6 +2589,10 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
   pv = (char*)(((size_t)pv + 3) & ~(size_t)3);
   float* fuS_f = reinterpret_cast<float*>(pv);
   unsigned short* fuS_h = reinterpret_cast<unsigned short*>(pv);
+  // pref[nw] u16: per-bitmap-word exclusive prefix count (slot of a
+  // column = pref[word] + popcount of the word's lower bits)
+  unsigned short* pref = reinterpret_cast<unsigned short*>(
+      pv + (size_t)cap * (BF16 ? 2 : 4));
   __shared__ int scan[NWAVE];
   __shared__ float s_lad[MAX_LS];
   __shared__ double cllh[16][MAX_LS];
@@ -2652,6 +2657,7 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
   int pos = wbase + incl - cnt;
   for (int wv = w0; wv < w1; ++wv) {
     u32 bits = bmap[wv];
+    pref[wv] = (unsigned short)pos;
     while (bits) {
       const int b = __ffs(bits) - 1;
       bits &= bits - 1;
@@ -2670,16 +2676,10 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
   {  // staged column ids -> compact positions, in place
     const int total = (int)(epos[e1] - p0);
     for (int i = tid; i < total; i += BLOCK) {
-      const unsigned short k = nidx[i];
-      int lo = 0, hi = ns;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (kS[mid] < k)
-          lo = mid + 1;
-        else
-          hi = mid;
-      }
-      nidx[i] = (unsigned short)lo;  // always found: k came from bmap
+      const int k = (int)nidx[i];  // always present: k came from bmap
+      const int wv = k >> 5;
+      nidx[i] = (unsigned short)((int)pref[wv] +
+                                 __popc(bmap[wv] & ((1u << (k & 31)) - 1u)));
     }
   }
   __syncthreads();
@@ -2816,6 +2816,283 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
   } else if (tid == 0) {
     best[u] = 0.f;
   }
+}
+
+// KFW: the KFS computation with ONE WAVE per node, for the routed nodes
+// whose bound (own support + staged neighbour entries) fits `wcap`.  On
+// the headline graph (mean degree 5.5) a 256-thread KFS block leaves most
+// lanes idle and pays ten block barriers per node; a one-wave workgroup
+// has no cross-wave synchronisation at all (__syncthreads() is only an
+// LDS wait here) and a CU holds 4x as many nodes in flight.  Differences
+// from KFS, same formulas / fp32-fp64 split / clamps otherwise:
+//   * per-edge (base, count) pairs are computed once from epos and kept
+//     in LDS (first KFW_ECAP edges; later edges of a rare wide node
+//     re-read epos) — no int64 epos reads inside the phase loops;
+//   * staged column -> slot by RANK: per-word exclusive prefix + popcount
+//     of the lower bits (two LDS reads, no binary search);
+//   * own row values come from the node's support list (contiguous)
+//     rather than a per-column gather from the F row;
+//   * dots run 4 edges at a time on 16-lane groups, the scatter into gacc
+//     runs edge by edge in CSR order as a plain LDS read-add-write (the
+//     columns of one edge are distinct) — no float atomics, so the
+//     results are bitwise reproducible;
+//   * sumF at the active columns is kept in LDS (sfS) for the trial
+//     phase's node terms; the finalized gradient overwrites gacc in place;
+//   * trials: lanes = 4 edge slots x 16 candidates, combined by
+//     __shfl_xor 16 then 32.
+// LDS = bitmap K/32 words + u16 prefix per word + wcap*(16|20) bytes +
+// the edge table: 5.3 KB at K=5000 bf16 with wcap=256.  Measured in
+// profiles/r05_kfs_wave.md.
+
+#define KFW_ECAP 64
+
+template <bool BF16>
+__global__ void __launch_bounds__(WAVE) kfw_sparse_t(
+    int K, const long long* __restrict__ indptr,
+    const int* __restrict__ indices, const float* __restrict__ sumF,
+    const int* __restrict__ order, int blk0,
+    const long long* __restrict__ soffset, const int* __restrict__ sidx,
+    const float* __restrict__ sval, const int* __restrict__ scount,
+    const long long* __restrict__ epos, const long long* __restrict__ goffset,
+    int* __restrict__ gidx, float* __restrict__ gval,
+    int* __restrict__ gcount, double* __restrict__ llh,
+    const float* __restrict__ GGp, const float* __restrict__ ladder,
+    float* __restrict__ best, int n_ladder, int wcap, float alpha,
+    float min_p, float max_p, float min_f, float max_f) {
+  const int b = blk0 + (int)blockIdx.x;  // position in the routed order
+  const int u = order[b];
+  const long long e0 = indptr[u];
+  const int deg = (int)(indptr[u + 1] - e0);
+  const int lane = threadIdx.x;
+  const int grp = lane >> 4;  // edge slot 0..3
+  const int gl = lane & 15;   // lane in group == candidate
+  const int nw = (K + 31) >> 5;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  // layout: bmap[nw] u32 | gacc[wcap] f32 | sfS[wcap] f32 | ebs[ECAP] u32
+  //         | (fp32: nval[wcap] fuS[wcap]) | nidx[wcap] u16 | kS[wcap] u16
+  //         | pref[nw] u16 | (bf16: nval[wcap] fuS[wcap] u16)
+  u32* bmap = reinterpret_cast<u32*>(smem);
+  float* gacc = reinterpret_cast<float*>(bmap + nw);
+  float* sfS = gacc + wcap;
+  u32* ebs = reinterpret_cast<u32*>(sfS + wcap);
+  float* nval_f = reinterpret_cast<float*>(ebs + KFW_ECAP);
+  float* fuS_f = nval_f + wcap;
+  unsigned short* nidx = reinterpret_cast<unsigned short*>(
+      BF16 ? nval_f : fuS_f + wcap);
+  unsigned short* kS = nidx + wcap;
+  unsigned short* pref = kS + wcap;
+  unsigned short* nval_h = pref + ((nw + 1) & ~1);
+  unsigned short* fuS_h = nval_h + wcap;
+
+  // edge table: (staging base << 16) | list length, from the epos prefix
+  const long long p0 = epos[e0];
+  if (lane < deg) {  // KFW_ECAP == WAVE: one pass
+    const long long a = epos[e0 + lane];
+    ebs[lane] = ((u32)(a - p0) << 16) | (u32)(epos[e0 + lane + 1] - a);
+  }
+  for (int i = lane; i < nw; i += WAVE) bmap[i] = 0u;
+  __syncthreads();
+  auto edge_bs = [&](int i) -> u32 {
+    if (i < KFW_ECAP) return ebs[i];
+    const long long a = epos[e0 + i];
+    return ((u32)(a - p0) << 16) | (u32)(epos[e0 + i + 1] - a);
+  };
+
+  // phase 1: stage neighbour lists, 4 edges at a time (16 lanes per
+  // edge), OR support bits
+  for (int et = 0; et < deg; et += 4) {
+    const int ei = et + grp;
+    if (ei < deg) {
+      const u32 bs = edge_bs(ei);
+      const int base = (int)(bs >> 16);
+      const int sv = (int)(bs & 0xffffu);
+      if (sv) {
+        const long long off = soffset[indices[e0 + ei]];
+        for (int j = gl; j < sv; j += 16) {
+          const int k = sidx[off + j];
+          nidx[base + j] = (unsigned short)k;
+          if (BF16)
+            nval_h[base + j] = pack1_bf16_rne(sval[off + j]);
+          else
+            nval_f[base + j] = sval[off + j];
+          atomicOr(&bmap[k >> 5], 1u << (k & 31));
+        }
+      }
+    }
+  }
+  const long long offu = soffset[u];
+  const int su = scount[u];
+  for (int j = lane; j < su; j += WAVE) {
+    const int k = sidx[offu + j];
+    atomicOr(&bmap[k >> 5], 1u << (k & 31));
+  }
+  __syncthreads();
+
+  // phase 1.5: bitmap scan -> sorted compact kS, per-word exclusive
+  // prefix, zeroed gacc/fuS slots
+  const int wchunk = (nw + WAVE - 1) / WAVE;
+  const int w0 = min(lane * wchunk, nw);
+  const int w1 = min(w0 + wchunk, nw);
+  int cnt = 0;
+  for (int wv = w0; wv < w1; ++wv) cnt += __popc(bmap[wv]);
+  int incl = cnt;
+#pragma unroll
+  for (int off = 1; off < WAVE; off <<= 1) {
+    const int v = __shfl_up(incl, off, WAVE);
+    if (lane >= off) incl += v;
+  }
+  const int ns = __shfl(incl, WAVE - 1, WAVE);
+  {
+    int pos = incl - cnt;
+    for (int wv = w0; wv < w1; ++wv) {
+      u32 bits = bmap[wv];
+      pref[wv] = (unsigned short)pos;
+      while (bits) {
+        const int bb = __ffs(bits) - 1;
+        bits &= bits - 1;
+        kS[pos] = (unsigned short)((wv << 5) + bb);
+        if (BF16)
+          fuS_h[pos] = 0;
+        else
+          fuS_f[pos] = 0.f;
+        gacc[pos] = 0.f;
+        ++pos;
+      }
+    }
+  }
+  __syncthreads();
+  auto rank_of = [&](int k) -> int {
+    const int wv = k >> 5;
+    return (int)pref[wv] + __popc(bmap[wv] & ((1u << (k & 31)) - 1u));
+  };
+  // own row values into their slots (from the node's own support list)
+  for (int j = lane; j < su; j += WAVE) {
+    const int p_ = rank_of(sidx[offu + j]);
+    if (BF16)
+      fuS_h[p_] = pack1_bf16_rne(sval[offu + j]);
+    else
+      fuS_f[p_] = sval[offu + j];
+  }
+  {  // staged column ids -> slot positions, in place
+    const int total = (int)(epos[e0 + deg] - p0);
+    for (int i = lane; i < total; i += WAVE)
+      nidx[i] = (unsigned short)rank_of((int)nidx[i]);
+  }
+  __syncthreads();
+
+  // phase 2: dots on 16-lane groups (4 edges at a time), then the
+  // w-weighted scatter edge by edge in CSR order (plain read-add-write:
+  // one edge's columns are distinct, the wave's LDS ops stay in order)
+  double llh_acc = 0.0;
+  for (int et = 0; et < deg; et += 4) {
+    const int ei = et + grp;
+    int base = 0, sv = 0;
+    if (ei < deg) {
+      const u32 bs = edge_bs(ei);
+      base = (int)(bs >> 16);
+      sv = (int)(bs & 0xffffu);
+    }
+    float part = 0.f;
+    for (int j = gl; j < sv; j += 16) {
+      const int p_ = (int)nidx[base + j];
+      const float fv = BF16 ? vget<true>(nval_h[base + j]) : nval_f[base + j];
+      const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
+      part += fu * fv;
+    }
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) part += __shfl_xor(part, off, WAVE);
+    const float x = part;
+    const float p = clamp_p(__expf(-x), min_p, max_p);
+    const float w = 1.f / (1.f - p);
+    if (ei < deg && gl == 0) llh_acc += (double)log1pf(-p) + (double)x;
+    const int nq = min(4, deg - et);
+    for (int q = 0; q < nq; ++q) {
+      const int bq = __shfl(base, q << 4, WAVE);
+      const int sq = __shfl(sv, q << 4, WAVE);
+      const float wq = __shfl(w, q << 4, WAVE);
+      for (int j = lane; j < sq; j += WAVE) {
+        const int p_ = (int)nidx[bq + j];
+        const float fv = BF16 ? vget<true>(nval_h[bq + j]) : nval_f[bq + j];
+        gacc[p_] += wq * fv;
+      }
+    }
+  }
+  __syncthreads();
+
+  // phase 3: finalize g in place over the compact set + write the global
+  // pools; node terms fs/ff and gg accumulate alongside
+  const long long go = goffset[b];
+  float gg_p = 0.f, fs_p = 0.f, ff_p = 0.f;
+  for (int i = lane; i < ns; i += WAVE) {
+    const int k = (int)kS[i];
+    const float f = BF16 ? vget<true>(fuS_h[i]) : fuS_f[i];
+    const float sfk = sumF[k];
+    const float g = gacc[i] - sfk + f;
+    gacc[i] = g;
+    sfS[i] = sfk;
+    gidx[go + i] = k;
+    gval[go + i] = g;
+    gg_p += g * g - sfk * sfk;
+    fs_p = fmaf(f, sfk, fs_p);
+    ff_p = fmaf(f, f, ff_p);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    gg_p += __shfl_xor(gg_p, off, WAVE);
+    fs_p += __shfl_xor(fs_p, off, WAVE);
+    ff_p += __shfl_xor(ff_p, off, WAVE);
+    llh_acc += __shfl_xor(llh_acc, off, WAVE);
+  }
+  const double llh_base = llh_acc + (double)(-fs_p) + (double)ff_p;
+  const float gg = gg_p + GGp[0];
+  if (lane == 0) {
+    gcount[b] = ns;
+    llh[u] = llh_base;
+  }
+  __syncthreads();
+
+  // phase 4: 16-candidate trials, lane (edge slot, candidate) serially
+  // accumulates one edge's trial dot; node terms striped over the slots
+  const bool live = gl < n_ladder;
+  const float sj = live ? ladder[gl] : 0.f;
+  double myllh = 0.0;
+  for (int et = 0; et < deg; et += 4) {
+    const int ei = et + grp;
+    if (ei < deg && live) {
+      const u32 bs = edge_bs(ei);
+      const int base = (int)(bs >> 16);
+      const int sv = (int)(bs & 0xffffu);
+      float x = 0.f;
+      for (int t = 0; t < sv; ++t) {
+        const int p_ = (int)nidx[base + t];
+        const float fv = BF16 ? vget<true>(nval_h[base + t]) : nval_f[base + t];
+        const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
+        const float c =
+            __builtin_amdgcn_fmed3f(fmaf(sj, gacc[p_], fu), min_f, max_f);
+        x = fmaf(c, fv, x);
+      }
+      const float p = clamp_p(__expf(-x), min_p, max_p);
+      myllh += (double)log1pf(-p) + (double)x;
+    }
+  }
+  float mynt = 0.f;
+  if (live) {
+    for (int i = grp; i < ns; i += 4) {
+      const float fu = BF16 ? vget<true>(fuS_h[i]) : fuS_f[i];
+      const float c =
+          __builtin_amdgcn_fmed3f(fmaf(sj, gacc[i], fu), min_f, max_f);
+      mynt = fmaf(c, fu - sfS[i], mynt);
+    }
+  }
+  myllh += __shfl_xor(myllh, 16, WAVE);
+  mynt += __shfl_xor(mynt, 16, WAVE);
+  myllh += __shfl_xor(myllh, 32, WAVE);
+  mynt += __shfl_xor(mynt, 32, WAVE);
+  const bool ok = live && (myllh + (double)mynt >=
+                           llh_base + (double)(alpha * sj * gg));
+  const unsigned long long bal = __ballot(ok) & 0xffffull;
+  const float spick = __shfl(sj, bal ? __ffsll(bal) - 1 : 0, WAVE);
+  if (lane == 0) best[u] = bal ? spick : 0.f;
 }
 
 // K3S also REWRITES the committed row's persistent support list
@@ -3495,7 +3772,7 @@ extern "C" void launch_kfs(const void* F, int bf16,
                            float min_f, float max_f, hipStream_t stream) {
   if (n_blocks == 0) return;
   if (n_ladder > 16) throw std::runtime_error("ladder length > 16 unsupported");
-  const size_t lds = ((K + 31) / 32) * 4 + (size_t)cap * (bf16 ? 16 : 20)
+  const size_t lds = ((K + 31) / 32) * 6 + (size_t)cap * (bf16 ? 16 : 20)
                      + 16;
   const char* ph = getenv("BIGCLAM_KFS_PHASES");  // measurement bisect only
   const int phases = ph ? atoi(ph) : 0xF;
@@ -3513,6 +3790,48 @@ extern "C" void launch_kfs(const void* F, int bf16,
                        soffset, sidx, sval, scount, epos, goffset, gidx,
                        gval, gcount, llh, GGp, ladder, best, n_ladder, cap,
                        alpha, min_p, max_p, min_f, max_f, phases);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// KFW LDS bytes for (K, wcap): bitmap + u16 prefix + wcap*(16|20) + the
+// edge table.  Exposed so the host clamps wcap to the workgroup budget.
+extern "C" long long kfw_lds_bytes(int bf16, int K, int wcap) {
+  const long long nw = (K + 31) / 32;
+  return nw * 4 + ((nw + 1) & ~1LL) * 2 + (long long)wcap * (bf16 ? 16 : 20) +
+         KFW_ECAP * 4;
+}
+
+extern "C" void launch_kfw(int bf16, const long long* indptr,
+                           const int* indices, const float* sumF,
+                           const int* order, int blk0, int n_blocks,
+                           const long long* soffset, const int* sidx,
+                           const float* sval, const int* scount,
+                           const long long* epos, const long long* goffset,
+                           int* gidx, float* gval, int* gcount, double* llh,
+                           const float* GGp, const float* ladder,
+                           float* best, int n_ladder, int wcap, int K,
+                           float alpha, float min_p, float max_p,
+                           float min_f, float max_f, hipStream_t stream) {
+  if (n_blocks == 0) return;
+  if (n_ladder > 16) throw std::runtime_error("ladder length > 16 unsupported");
+  const size_t lds = (size_t)kfw_lds_bytes(bf16, K, wcap);
+  if (lds > 160 * 1024)
+    throw std::runtime_error("KFW: wcap exceeds the workgroup LDS budget");
+  if (bf16) {
+    allow_large_lds((const void*)&kfw_sparse_t<true>, lds);
+    hipLaunchKernelGGL((kfw_sparse_t<true>), dim3(n_blocks), dim3(WAVE), lds,
+                       stream, K, indptr, indices, sumF, order, blk0,
+                       soffset, sidx, sval, scount, epos, goffset, gidx,
+                       gval, gcount, llh, GGp, ladder, best, n_ladder, wcap,
+                       alpha, min_p, max_p, min_f, max_f);
+  } else {
+    allow_large_lds((const void*)&kfw_sparse_t<false>, lds);
+    hipLaunchKernelGGL((kfw_sparse_t<false>), dim3(n_blocks), dim3(WAVE), lds,
+                       stream, K, indptr, indices, sumF, order, blk0,
+                       soffset, sidx, sval, scount, epos, goffset, gidx,
+                       gval, gcount, llh, GGp, ladder, best, n_ladder, wcap,
+                       alpha, min_p, max_p, min_f, max_f);
   }
   HIP_CHECK(hipGetLastError());
 }

@@ -366,6 +366,14 @@ extern "C" void launch_kfs(const void*, int, const long long*, const int*,
                            int*, double*, const float*, const float*,
                            float*, int, int, int, float, float, float,
                            float, float, hipStream_t);
+extern "C" void launch_kfw(int, const long long*, const int*, const float*,
+                           const int*, int, int, const long long*,
+                           const int*, const float*, const int*,
+                           const long long*, const long long*, int*, float*,
+                           int*, double*, const float*, const float*,
+                           float*, int, int, int, float, float, float,
+                           float, float, hipStream_t);
+extern "C" long long kfw_lds_bytes(int, int, int);
 extern "C" void launch_k3s(void*, int, const int*, int, const long long*,
                            const int*, const float*, const int*,
                            const float*, const long long*, int*, float*,
@@ -407,7 +415,11 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
                   torch::Tensor gval, torch::Tensor gcount,
                   torch::Tensor llh, torch::Tensor GG, torch::Tensor ladder,
                   torch::Tensor best, int64_t cap, double alpha,
-                  double min_p, double max_p, double min_f, double max_f) {
+                  double min_p, double max_p, double min_f, double max_f,
+                  int64_t n_block, int64_t wcap) {
+  // order[:n_block] runs the block kernel (KFS), order[n_block:] the
+  // one-wave-per-node kernel (KFW, bound <= wcap); pools and gcount are
+  // indexed by position in `order` for both
   CHECK_F(F);
   CHECK_IN(indptr, torch::kInt64);
   CHECK_IN(indices, torch::kInt32);
@@ -429,10 +441,27 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
   const int n_blocks = (int)order.size(0);
   TORCH_CHECK(goffset.size(0) >= n_blocks && gcount.size(0) >= n_blocks);
   TORCH_CHECK(epos.size(0) == indices.size(0) + 1, "epos must be nnz+1");
+  TORCH_CHECK(n_block >= 0 && n_block <= n_blocks, "n_block out of range");
+  const int n_wave = n_blocks - (int)n_block;
+  TORCH_CHECK(n_wave == 0 || (wcap > 0 && wcap <= cap),
+              "wave class needs 0 < wcap <= cap");
+  if (n_wave > 0)
+    launch_kfw(is_bf16(F) ? 1 : 0,
+               reinterpret_cast<const long long*>(indptr.data_ptr<int64_t>()),
+               indices.data_ptr<int>(), sumF.data_ptr<float>(),
+               order.data_ptr<int>(), (int)n_block, n_wave, i64p(soffset),
+               sidx.data_ptr<int>(), sval.data_ptr<float>(),
+               scount.data_ptr<int>(), i64p(epos), i64p(goffset),
+               gidx.data_ptr<int>(), gval.data_ptr<float>(),
+               gcount.data_ptr<int>(), llh.data_ptr<double>(),
+               GG.data_ptr<float>(), ladder.data_ptr<float>(),
+               best.data_ptr<float>(), (int)ladder.size(0), (int)wcap,
+               (int)F.size(1), (float)alpha, (float)min_p, (float)max_p,
+               (float)min_f, (float)max_f, current_stream());
   launch_kfs(F.data_ptr(), is_bf16(F) ? 1 : 0,
              reinterpret_cast<const long long*>(indptr.data_ptr<int64_t>()),
              indices.data_ptr<int>(), sumF.data_ptr<float>(),
-             order.data_ptr<int>(), n_blocks,
+             order.data_ptr<int>(), (int)n_block,
              reinterpret_cast<const long long*>(soffset.data_ptr<int64_t>()),
              sidx.data_ptr<int>(), sval.data_ptr<float>(),
              scount.data_ptr<int>(),
@@ -668,8 +697,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sparse_support", &sparse_support,
         "KAF: per-row support compaction of F (count or fill pass)");
   m.def("sparse_fused", &sparse_fused,
-        "KFS: fused compact gradient + 16-candidate Armijo for routed "
-        "nodes (LDS bitmap active sets)");
+        "KFS/KFW: fused compact gradient + 16-candidate Armijo for routed "
+        "nodes (LDS bitmap active sets); order[:n_block] one block per "
+        "node, order[n_block:] one wave per node");
+  m.def("sparse_wave_lds_bytes",
+        [](bool bf16, int64_t K, int64_t wcap) {
+          return (int64_t)kfw_lds_bytes(bf16 ? 1 : 0, (int)K, (int)wcap);
+        },
+        "KFW dynamic LDS bytes at (dtype, padded K, wcap)");
   m.def("sparse_colsum", &sparse_colsum,
         "list-based column sums (sparse path; stale/over-cap rows dense)");
   m.def("sparse_commit", &sparse_commit,

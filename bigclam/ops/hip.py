@@ -273,14 +273,21 @@ def sparse_sweep_part(
     best_out: torch.Tensor,
     cfg: BigClamConfig,
     state_pools=None,
+    n_block: int = None,
+    wcap: int = 0,
 ):
-    """KFS for the routed (sparse) nodes: one fused launch computing the
-    compact gradient pools, llh per node, and the Armijo best step.
-    Writes llh_out/best_out at the routed node positions; returns the
-    commit pack for K3S."""
+    """KFS/KFW for the routed (sparse) nodes: the compact gradient pools,
+    llh per node, and the Armijo best step.  ``order_sparse[:n_block]``
+    (bound in (wcap, cap]) runs one block per node, the rest (bound <=
+    wcap) one wave per node; ``n_block=None`` sends every node to the
+    block kernel.  Pools, goffset and gcount are indexed by position in
+    ``order_sparse`` for both.  Writes llh_out/best_out at the routed
+    node positions; returns the commit pack for K3S."""
     ext = ensure_loaded()
     dev = F.device
     n_s = int(order_sparse.numel())
+    if n_block is None:
+        n_block = n_s
     # per-STATE grad pools (via state_pools): the commit consumes them at
     # the START of the next sweep (the pipelined carry), so a shared
     # module pool could be clobbered by another coexisting state
@@ -291,6 +298,7 @@ def sparse_sweep_part(
         F, indptr, indices, sumF, order_sparse, soffset, sidx, sval, scount,
         epos, goffset, gidx, gval, gcount, llh_out, GG, _ladder(cfg, dev),
         best_out, cap, cfg.alpha, cfg.min_p, cfg.max_p, cfg.min_f, cfg.max_f,
+        int(n_block), int(wcap),
     )
     return {
         "order": order_sparse,
