@@ -139,6 +139,9 @@ class ShardState:
         self._sp_cap: Optional[int] = None
         self._dirty: Optional[torch.Tensor] = None  # uint8 [n_rows]
         self._kaf_valid = False  # persistent support lists match F
+        # local rows the next KAF may have to rescan (the dense class of
+        # the last routed commit); None = unknown, scan the full grid
+        self._kaf_rows: Optional[torch.Tensor] = None
         self._side_stream = None  # hub-remainder overlap (sparse path)
         self._class_edges = None  # routing-class boundaries (device, u8)
         # per-edge source row (torch reference path); built lazily on CPU
@@ -194,6 +197,7 @@ class ShardState:
     def set_local_F(self, F_local: torch.Tensor):
         """Install owned rows (true-K width) and (re)compute the global sumF."""
         self._kaf_valid = False
+        self._kaf_rows = None
         self.F = torch.zeros(
             self.shard.n_rows,
             self.kp,
@@ -547,6 +551,7 @@ class ShardState:
             )
             self._dirty = torch.ones(n_rows, device=dev, dtype=torch.uint8)
             self._kaf_valid = False
+            self._kaf_rows = None
         soffset = self._sp_soffset
         scount = self._sp_scount
         sidx = self._sp_sidx
@@ -562,9 +567,28 @@ class ShardState:
             dirty = self._dirty
         else:
             dirty = torch.empty(0, device=dev, dtype=torch.uint8)
+            self._kaf_rows = None
         ext = ops.ensure_loaded()
         n_loc = self.n_local
-        if halo_work is not None and n_rows > n_loc:
+        if self._kaf_rows is not None:
+            # list mode: the last routed commit left dirty flags only on
+            # its dense class, so the local section launches one block
+            # per row of that class instead of a full grid of blocks that
+            # return at once.  Halo rows: full, no mask (as below).
+            ext.sparse_support(
+                self.F[:n_loc], soffset[:n_loc], scount[:n_loc], sidx,
+                sval, cap, True, dirty[:n_loc], self._kaf_rows,
+            )
+            if halo_work is not None:
+                halo_work.wait()
+                halo_work = None
+            if n_rows > n_loc:
+                ext.sparse_support(
+                    self.F[n_loc:], soffset[n_loc:], scount[n_loc:], sidx,
+                    sval, cap, True,
+                    torch.empty(0, device=dev, dtype=torch.uint8),
+                )
+        elif halo_work is not None and n_rows > n_loc:
             ext.sparse_support(
                 self.F[:n_loc], soffset[:n_loc], scount[:n_loc], sidx,
                 sval, cap, True,
@@ -663,14 +687,23 @@ class ShardState:
             n_block=n_blk, wcap=wcap,
         )
         pack["n_block"] = n_blk  # order[:n_block] block class, rest wave
+        pack["wcap"] = wcap
         if n_d:
             torch.cuda.current_stream(dev).wait_stream(self._side_stream)
         pack["best"] = best
-        # dense commit must skip sparse rows (their grad rows are unset)
-        steps_dense = best.clone()
-        steps_dense[order_s.long()] = 0.0
-        pack["steps_dense"] = steps_dense
+        # the dense commit must skip the routed rows (their grad rows are
+        # unset): it runs over this list only, with the full `best`
+        pack["order_d"] = order_d
         return grad, llh, best, pack
+
+    @staticmethod
+    def _steps_dense(pack):
+        """``best`` with the routed rows zeroed: the step vector of a
+        full-grid dense commit after a routed one (fallback branches
+        only; the hot path commits ``pack["order_d"]`` in list mode)."""
+        steps = pack["best"].clone()
+        steps[pack["order"].long()] = 0.0
+        return steps
 
     def apply_commit(self, grad, steps, pack):
         """Commit a sweep's accepted steps: K3S for sparse-routed rows
@@ -678,21 +711,29 @@ class ShardState:
         reads the POST-commit F for every row)."""
         accepted = steps  # full best: sparse + dense accepted rows
         if pack is not None:
-            # K3S commits AND rewrites the sparse rows' support lists,
-            # so only DENSE-committed rows need a KAF rescan
+            # K3S/K3W commit AND rewrite the routed rows' support lists
+            # (and clear their dirty flags), so only DENSE-committed rows
+            # need a KAF rescan
             ops = _hip_ops()
             ops.sparse_commit(self.F_local, pack, pack["best"], self,
                               self.cfg)
-            steps = pack["steps_dense"]
             if self._kaf_valid and os.environ.get(
                 "BIGCLAM_SPARSE_COLSUM", "1"
             ) != "0":
                 # list-based sumF refresh: the persistent lists are
                 # current for everything except the dense-committed
                 # (dirty) and over-cap rows, which the kernel reads
-                # dense — exact for the current F, ~60x fewer bytes
-                ops.apply_step(self.F_local, grad, steps, self.cfg)
-                self._dirty[: self.n_local] = (steps > 0).to(torch.uint8)
+                # dense — exact for the current F, ~60x fewer bytes.
+                # The dense commit runs over the dense class only and
+                # sets those rows' dirty flags itself; every local row is
+                # in exactly one class, so _dirty[:n_local] is complete
+                # without a torch write.
+                order_d = pack["order_d"]
+                if order_d.numel():
+                    ops.apply_step(self.F_local, grad, pack["best"],
+                                   self.cfg, rows=order_d,
+                                   dirty=self._dirty)
+                self._kaf_rows = order_d
                 ns = (self.n_local + 511) // 512
                 if (
                     self._colsum_partials is None
@@ -710,8 +751,13 @@ class ShardState:
                 self.sumF = self._colsum_partials.sum(dim=0)
                 comm.all_reduce_(self.sumF)
                 return
+            # fallback (BIGCLAM_SPARSE_COLSUM=0): full-grid dense commit
+            # with the routed rows masked out of the step vector
+            steps = self._steps_dense(pack)
         self.apply_step(grad, steps)
-        # incremental KAF bookkeeping (halo rows stay always-dirty)
+        # incremental KAF bookkeeping (halo rows stay always-dirty); the
+        # mask is set from torch here, so the next KAF scans the full grid
+        self._kaf_rows = None
         if self._dirty is not None:
             dirty_rows = steps if pack is not None else accepted
             self._dirty[: self.n_local] = (dirty_rows > 0).to(torch.uint8)
@@ -781,6 +827,7 @@ class ShardState:
         (one read pass) keeps the sumF == colsum(F) invariant exact instead
         of accumulating incremental deltas."""
         self._kaf_valid = False  # re-validated by apply_commit
+        self._kaf_rows = None
         if self.use_hip and self.storage_dtype == torch.bfloat16:
             # fused commit + column sums: one pass over F (the separate
             # flow re-read F via an fp32 materialization, ~3.5 ms/sweep

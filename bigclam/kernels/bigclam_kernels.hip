@@ -596,13 +596,23 @@ __global__ void __launch_bounds__(BLOCK, 3) k2_ls_v3(
 // with an accepted step.  One block per node; rows with s==0 return without
 // touching memory.  sumF is recomputed afterwards (column sum + allreduce)
 // which keeps the sumF == colsum(F) invariant exact.
+//
+// List mode (rows != nullptr): the grid is the list length and block b
+// commits row rows[b]; rows not listed are never touched, whatever steps
+// holds for them.  The sparse path lists its dense class here, so the
+// routed rows' steps need no masking and no block is launched for them.
+// In list mode the kernel also records dirty[u] = (s > 0): the rows the
+// next KAF has to rescan.
 
 extern "C" __global__ void __launch_bounds__(BLOCK) k3_apply_step(
     float* __restrict__ F, const float* __restrict__ grad,
     const float* __restrict__ steps, int n_local, int K, float min_f,
-    float max_f) {
-  const int u = blockIdx.x;
+    float max_f, const int* __restrict__ rows,
+    unsigned char* __restrict__ dirty) {
+  const int u = rows ? rows[blockIdx.x] : (int)blockIdx.x;
+  if ((unsigned)u >= (unsigned)n_local) return;
   const float s = steps[u];
+  if (rows && dirty && threadIdx.x == 0) dirty[u] = s > 0.f;
   if (s <= 0.f) return;
   float* __restrict__ fu = F + (size_t)u * K;
   const float* __restrict__ gu = grad + (size_t)u * K;
@@ -2033,9 +2043,13 @@ __global__ void __launch_bounds__(BLOCK) k2_ls_v3_bf16(
 extern "C" __global__ void __launch_bounds__(BLOCK) k3_apply_step_bf16(
     u32* __restrict__ F, const float* __restrict__ grad,
     const float* __restrict__ steps, int n_local, int K, float min_f,
-    float max_f) {
-  const int u = blockIdx.x;
+    float max_f, const int* __restrict__ rows,
+    unsigned char* __restrict__ dirty) {
+  // list mode as in k3_apply_step
+  const int u = rows ? rows[blockIdx.x] : (int)blockIdx.x;
+  if ((unsigned)u >= (unsigned)n_local) return;
   const float s = steps[u];
+  if (rows && dirty && threadIdx.x == 0) dirty[u] = s > 0.f;
   if (s <= 0.f) return;
   u32* __restrict__ fu = F + (size_t)u * (K / 2);
   const float* __restrict__ gu = grad + (size_t)u * K;
@@ -2421,7 +2435,9 @@ __global__ void __launch_bounds__(BLOCK) kw_grad_t(
 //                      compact lists: candidates clamp(fu + s_j·g) are
 //                      supported on S_u exactly, so trial dots walk the
 //                      neighbor lists with a binary search into S_u.
-//   K3S k3s_commit_t   sparse projected commit (writes confined to S_u).
+//   K3S k3s_commit_t   sparse projected commit (writes confined to S_u),
+//                      one block per node; K3W k3w_commit_t the same with
+//                      one wave per node for the wave class.
 //
 // Routing is exact and per node: bound_u = s_u + Σ_{v∈N(u)} s_v ≥ |S_u|
 // (host-side from KAF counts); nodes with bound ≤ cap take this path,
@@ -2448,10 +2464,13 @@ __global__ void __launch_bounds__(BLOCK) kaf_support_t(
     const void* __restrict__ Fp, int n_rows, int K, int ldF, int cap,
     const long long* __restrict__ soffset, int* __restrict__ scount,
     int* __restrict__ sidx, float* __restrict__ sval,
-    const unsigned char* __restrict__ dirty) {
+    const unsigned char* __restrict__ dirty, const int* __restrict__ rows) {
   __shared__ int scan[BLOCK];
-  const int r = blockIdx.x;
-  if (r >= n_rows) return;
+  // list mode (rows != nullptr): the grid is the list length and block b
+  // scans row rows[b] — the rows the last commit's dense class covered,
+  // the only local rows whose dirty flag can be set
+  const int r = rows ? rows[blockIdx.x] : (int)blockIdx.x;
+  if ((unsigned)r >= (unsigned)n_rows) return;
   // incremental mode: rows unchanged since the last commit keep their
   // persistent counts/lists (the commit kernels only touch accepted
   // rows; halo rows are always marked dirty at ws > 1)
@@ -3107,9 +3126,13 @@ __global__ void __launch_bounds__(BLOCK) k3s_commit_t(
     const float* __restrict__ gval, const int* __restrict__ gcount,
     const float* __restrict__ best, const long long* __restrict__ soffset,
     int* __restrict__ sidx, float* __restrict__ sval,
-    int* __restrict__ scount, int cap, float min_f, float max_f) {
+    int* __restrict__ scount, unsigned char* __restrict__ dirty, int cap,
+    float min_f, float max_f) {
   __shared__ int scan[NWAVE];
   const int u = order[blockIdx.x];
+  // every routed position, accepted or not: its list is (or stays)
+  // current, so the next KAF and the list-based column sum skip the row
+  if (dirty != nullptr && threadIdx.x == 0) dirty[u] = 0;
   const float s = best[u];
   if (s <= 0.f) return;
   const int ns = gcount[blockIdx.x];
@@ -3165,6 +3188,69 @@ __global__ void __launch_bounds__(BLOCK) k3s_commit_t(
       ++w;
     }
   }
+}
+
+// K3W: the same commit and list rewrite for the WAVE class, one wave per
+// node (four nodes per 256-thread block).  The routed order is laid out
+// [block | wave], so wave w serves pack position blk0 + w, as KFW does.
+// Invariant: a wave-class node has ns = gcount <= bound <= wcap <= cap
+// (routing + KFW; the binding checks wcap <= cap), so the rewritten list
+// (a subset of the ns active entries) always fits its cap-strided slot —
+// no over-cap branch.  Single pass, in rounds of 64 consecutive entries:
+// each lane commits its entry and keeps the new value in a register; the
+// list slot is the running count plus the rank of the lane among the
+// round's non-zero lanes (ballot + popcount).  Rounds ascend and gidx is
+// ascending, so the list stays ascending in k.  No LDS, no barrier, no
+// second read of F, no atomics: deterministic, and element-wise the same
+// arithmetic as K3S (bitwise-equal F, scount and lists).
+template <bool BF16>
+__global__ void __launch_bounds__(BLOCK) k3w_commit_t(
+    void* __restrict__ Fp, int ldF, const int* __restrict__ order, int blk0,
+    int n_wave, const long long* __restrict__ goffset,
+    const int* __restrict__ gidx, const float* __restrict__ gval,
+    const int* __restrict__ gcount, const float* __restrict__ best,
+    const long long* __restrict__ soffset, int* __restrict__ sidx,
+    float* __restrict__ sval, int* __restrict__ scount,
+    unsigned char* __restrict__ dirty, float min_f, float max_f) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int w = blockIdx.x * NWAVE + (threadIdx.x >> 6);
+  if (w >= n_wave) return;  // tail waves of the last block (wave-uniform)
+  const int b = blk0 + w;
+  const int u = order[b];
+  if (dirty != nullptr && lane == 0) dirty[u] = 0;
+  const float s = best[u];
+  if (s <= 0.f) return;  // wave-uniform: F and the lists stay untouched
+  const int ns = gcount[b];
+  const long long go = goffset[b];
+  const long long so = soffset[u];
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int running = 0;
+  for (int base = 0; base < ns; base += WAVE) {
+    const int i = base + lane;
+    int k = 0;
+    float nf = 0.f;
+    if (i < ns) {
+      k = gidx[go + i];
+      const float f = f_elem<BF16>(Fp, ldF, u, k);
+      nf = __builtin_amdgcn_fmed3f(fmaf(s, gval[go + i], f), min_f, max_f);
+      if (BF16) {
+        const unsigned short h = pack1_bf16_rne(nf);
+        reinterpret_cast<unsigned short*>(Fp)[(size_t)u * ldF + k] = h;
+        nf = __uint_as_float((u32)h << 16);  // post-round value
+      } else {
+        reinterpret_cast<float*>(Fp)[(size_t)u * ldF + k] = nf;
+      }
+    }
+    const bool keep = nf != 0.f;  // lanes past ns hold 0
+    const unsigned long long bal = __ballot(keep);
+    if (keep) {
+      const long long at = so + running + __popcll(bal & below);
+      sidx[at] = k;
+      sval[at] = nf;
+    }
+    running += __popcll(bal);
+  }
+  if (lane == 0) scount[u] = running;
 }
 
 // ------------------------------------------------- list-based column sum
@@ -3458,7 +3544,26 @@ extern "C" void launch_k3_bf16(void* F, const float* grad, const float* steps,
   if (n_local == 0) return;
   hipLaunchKernelGGL(k3_apply_step_bf16, dim3(n_local), dim3(256), 0, stream,
                      reinterpret_cast<u32*>(F), grad, steps, n_local, K,
-                     min_f, max_f);
+                     min_f, max_f, (const int*)nullptr,
+                     (unsigned char*)nullptr);
+  HIP_CHECK(hipGetLastError());
+}
+
+// List-mode K3 (fp32 and bf16): one block per entry of rows[0..n_list).
+extern "C" void launch_k3_rows(void* F, int bf16, const float* grad,
+                               const float* steps, int n_local, int K,
+                               float min_f, float max_f, const int* rows,
+                               int n_list, unsigned char* dirty,
+                               hipStream_t stream) {
+  if (n_list == 0) return;
+  if (bf16)
+    hipLaunchKernelGGL(k3_apply_step_bf16, dim3(n_list), dim3(256), 0, stream,
+                       reinterpret_cast<u32*>(F), grad, steps, n_local, K,
+                       min_f, max_f, rows, dirty);
+  else
+    hipLaunchKernelGGL(k3_apply_step, dim3(n_list), dim3(256), 0, stream,
+                       reinterpret_cast<float*>(F), grad, steps, n_local, K,
+                       min_f, max_f, rows, dirty);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -3549,7 +3654,8 @@ extern "C" void launch_k3(float* F, const float* grad, const float* steps,
                           hipStream_t stream) {
   if (n_local == 0) return;
   hipLaunchKernelGGL(k3_apply_step, dim3(n_local), dim3(256), 0, stream, F,
-                     grad, steps, n_local, K, min_f, max_f);
+                     grad, steps, n_local, K, min_f, max_f,
+                     (const int*)nullptr, (unsigned char*)nullptr);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -3738,12 +3844,15 @@ extern "C" void launch_k1_chunked(const void* F, int bf16,
 extern "C" void launch_kaf(const void* F, int bf16, int n_rows, int K,
                            int cap, const long long* soffset, int* scount,
                            int* sidx, float* sval, int fill,
-                           const unsigned char* dirty, hipStream_t stream) {
-  if (n_rows == 0) return;
+                           const unsigned char* dirty, const int* rows,
+                           int n_list, hipStream_t stream) {
+  // rows == nullptr: one block per row of F; else one per listed row
+  const int grid = rows ? n_list : n_rows;
+  if (grid == 0) return;
 #define KAF_CASE(B, FI)                                                     \
-  hipLaunchKernelGGL((kaf_support_t<B, FI>), dim3(n_rows), dim3(BLOCK), 0,  \
+  hipLaunchKernelGGL((kaf_support_t<B, FI>), dim3(grid), dim3(BLOCK), 0,    \
                      stream, F, n_rows, K, K, cap, soffset, scount, sidx,   \
-                     sval, dirty)
+                     sval, dirty, rows)
   if (bf16) {
     if (fill)
       KAF_CASE(true, true);
@@ -3836,22 +3945,40 @@ extern "C" void launch_kfw(int bf16, const long long* indptr,
   HIP_CHECK(hipGetLastError());
 }
 
-extern "C" void launch_k3s(void* F, int bf16, const int* order, int n_blocks,
-                           const long long* goffset, const int* gidx,
-                           const float* gval, const int* gcount,
-                           const float* best, const long long* soffset,
-                           int* sidx, float* sval, int* scount, int cap,
-                           int K, float min_f, float max_f,
-                           hipStream_t stream) {
-  if (n_blocks == 0) return;
+// Sparse commit of a routed order laid out [block | wave]: positions
+// [0, n_block) one block per node (K3S), [n_block, n_total) one wave per
+// node, four per workgroup (K3W).  dirty may be null (flags not kept).
+extern "C" void launch_k3s(void* F, int bf16, const int* order, int n_block,
+                           int n_total, const long long* goffset,
+                           const int* gidx, const float* gval,
+                           const int* gcount, const float* best,
+                           const long long* soffset, int* sidx, float* sval,
+                           int* scount, unsigned char* dirty, int cap, int K,
+                           float min_f, float max_f, hipStream_t stream) {
+  const int n_wave = n_total - n_block;
+  const int wgrid = (n_wave + NWAVE - 1) / NWAVE;
   if (bf16) {
-    hipLaunchKernelGGL((k3s_commit_t<true>), dim3(n_blocks), dim3(BLOCK), 0,
-                       stream, F, K, order, goffset, gidx, gval, gcount,
-                       best, soffset, sidx, sval, scount, cap, min_f, max_f);
+    if (n_block > 0)
+      hipLaunchKernelGGL((k3s_commit_t<true>), dim3(n_block), dim3(BLOCK), 0,
+                         stream, F, K, order, goffset, gidx, gval, gcount,
+                         best, soffset, sidx, sval, scount, dirty, cap, min_f,
+                         max_f);
+    if (n_wave > 0)
+      hipLaunchKernelGGL((k3w_commit_t<true>), dim3(wgrid), dim3(BLOCK), 0,
+                         stream, F, K, order, n_block, n_wave, goffset, gidx,
+                         gval, gcount, best, soffset, sidx, sval, scount,
+                         dirty, min_f, max_f);
   } else {
-    hipLaunchKernelGGL((k3s_commit_t<false>), dim3(n_blocks), dim3(BLOCK), 0,
-                       stream, F, K, order, goffset, gidx, gval, gcount,
-                       best, soffset, sidx, sval, scount, cap, min_f, max_f);
+    if (n_block > 0)
+      hipLaunchKernelGGL((k3s_commit_t<false>), dim3(n_block), dim3(BLOCK), 0,
+                         stream, F, K, order, goffset, gidx, gval, gcount,
+                         best, soffset, sidx, sval, scount, dirty, cap, min_f,
+                         max_f);
+    if (n_wave > 0)
+      hipLaunchKernelGGL((k3w_commit_t<false>), dim3(wgrid), dim3(BLOCK), 0,
+                         stream, F, K, order, n_block, n_wave, goffset, gidx,
+                         gval, gcount, best, soffset, sidx, sval, scount,
+                         dirty, min_f, max_f);
   }
   HIP_CHECK(hipGetLastError());
 }

@@ -4,6 +4,8 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
+#include <optional>
+
 extern "C" void launch_k1(const float*, const long long*, const int*,
                           const float*, const int*, float*, double*, int, int,
                           float, float, hipStream_t);
@@ -29,6 +31,9 @@ extern "C" void launch_k2_bf16(const void*, const long long*, const int*,
                                hipStream_t);
 extern "C" void launch_k3_bf16(void*, const float*, const float*, int, int,
                                float, float, hipStream_t);
+extern "C" void launch_k3_rows(void*, int, const float*, const float*, int,
+                               int, float, float, const int*, int,
+                               unsigned char*, hipStream_t);
 extern "C" void launch_k5(const long long*, const int*, double*, int, double,
                           hipStream_t);
 extern "C" void launch_kf(const float*, const long long*, const int*,
@@ -200,8 +205,14 @@ void linesearch(torch::Tensor F, torch::Tensor indptr, torch::Tensor indices,
   }
 }
 
+// rows given: list mode — only the listed rows are committed (grid = list
+// length, an empty list launches nothing), and dirty (uint8 [>= n_local],
+// optional) receives (steps[u] > 0) at every listed row.  The caller
+// guarantees 0 <= rows[i] < n_local.
 void apply_step(torch::Tensor F_local, torch::Tensor grad,
-                torch::Tensor steps, double min_f, double max_f) {
+                torch::Tensor steps, double min_f, double max_f,
+                std::optional<torch::Tensor> rows,
+                std::optional<torch::Tensor> dirty) {
   CHECK_F(F_local);
   CHECK_IN(grad, torch::kFloat32);
   CHECK_IN(steps, torch::kFloat32);
@@ -209,13 +220,31 @@ void apply_step(torch::Tensor F_local, torch::Tensor grad,
   const int K = (int)F_local.size(1);
   TORCH_CHECK(grad.size(0) == n_local && grad.size(1) == K);
   TORCH_CHECK(steps.size(0) == n_local);
+  TORCH_CHECK(K % (is_bf16(F_local) ? 8 : 4) == 0,
+              "K must be padded to a multiple of 8 (bf16) or 4 (fp32)");
+  if (rows.has_value()) {
+    const torch::Tensor& rl = *rows;
+    CHECK_IN(rl, torch::kInt32);
+    TORCH_CHECK(rl.dim() == 1 && rl.size(0) <= n_local);
+    unsigned char* dp = nullptr;
+    if (dirty.has_value()) {
+      TORCH_CHECK(dirty->is_cuda() && dirty->is_contiguous() &&
+                  dirty->scalar_type() == torch::kUInt8 &&
+                  dirty->size(0) >= n_local);
+      dp = dirty->data_ptr<uint8_t>();
+    }
+    launch_k3_rows(F_local.data_ptr(), is_bf16(F_local) ? 1 : 0,
+                   grad.data_ptr<float>(), steps.data_ptr<float>(), n_local,
+                   K, (float)min_f, (float)max_f, rl.data_ptr<int>(),
+                   (int)rl.size(0), dp, current_stream());
+    return;
+  }
+  TORCH_CHECK(!dirty.has_value(), "dirty is written in list mode only");
   if (is_bf16(F_local)) {
-    TORCH_CHECK(K % 8 == 0, "bf16 K must be padded to a multiple of 8");
     launch_k3_bf16(F_local.data_ptr(), grad.data_ptr<float>(),
                    steps.data_ptr<float>(), n_local, K, (float)min_f,
                    (float)max_f, current_stream());
   } else {
-    TORCH_CHECK(K % 4 == 0, "K must be padded to a multiple of 4");
     launch_k3(F_local.data_ptr<float>(), grad.data_ptr<float>(),
               steps.data_ptr<float>(), n_local, K, (float)min_f,
               (float)max_f, current_stream());
@@ -358,7 +387,8 @@ void edge_grad_llh_chunked(torch::Tensor F, torch::Tensor indptr,
 // Sparse-adaptive sweep (KAF/K1S/K2S/K3S — docs/sparse_sweep_design.md).
 extern "C" void launch_kaf(const void*, int, int, int, int,
                            const long long*, int*, int*, float*, int,
-                           const unsigned char*, hipStream_t);
+                           const unsigned char*, const int*, int,
+                           hipStream_t);
 extern "C" void launch_kfs(const void*, int, const long long*, const int*,
                            const float*, const int*, int, const long long*,
                            const int*, const float*, const int*,
@@ -374,10 +404,11 @@ extern "C" void launch_kfw(int, const long long*, const int*, const float*,
                            float*, int, int, int, float, float, float,
                            float, float, hipStream_t);
 extern "C" long long kfw_lds_bytes(int, int, int);
-extern "C" void launch_k3s(void*, int, const int*, int, const long long*,
-                           const int*, const float*, const int*,
-                           const float*, const long long*, int*, float*,
-                           int*, int, int, float, float, hipStream_t);
+extern "C" void launch_k3s(void*, int, const int*, int, int,
+                           const long long*, const int*, const float*,
+                           const int*, const float*, const long long*, int*,
+                           float*, int*, unsigned char*, int, int, float,
+                           float, hipStream_t);
 
 static const long long* i64p(const torch::Tensor& t) {
   return reinterpret_cast<const long long*>(t.data_ptr<int64_t>());
@@ -386,7 +417,11 @@ static const long long* i64p(const torch::Tensor& t) {
 void sparse_support(torch::Tensor F, torch::Tensor soffset,
                     torch::Tensor scount, torch::Tensor sidx,
                     torch::Tensor sval, int64_t cap, bool fill,
-                    torch::Tensor dirty) {
+                    torch::Tensor dirty,
+                    std::optional<torch::Tensor> rows) {
+  // rows given: list mode — one block per listed row (still subject to
+  // the dirty mask); an empty list launches nothing.  The caller
+  // guarantees 0 <= rows[i] < n_rows (the kernel drops anything above).
   CHECK_F(F);
   CHECK_IN(soffset, torch::kInt64);
   CHECK_IN(scount, torch::kInt32);
@@ -401,9 +436,20 @@ void sparse_support(torch::Tensor F, torch::Tensor soffset,
                 dirty.is_contiguous() && dirty.size(0) == n_rows);
     dp = dirty.data_ptr<uint8_t>();
   }
+  const int* rp = nullptr;
+  int n_list = 0;
+  if (rows.has_value()) {
+    const torch::Tensor& rl = *rows;
+    CHECK_IN(rl, torch::kInt32);
+    TORCH_CHECK(rl.dim() == 1);
+    n_list = (int)rl.size(0);
+    if (n_list == 0) return;
+    rp = rl.data_ptr<int>();
+  }
   launch_kaf(F.data_ptr(), is_bf16(F) ? 1 : 0, n_rows, K, (int)cap,
              i64p(soffset), scount.data_ptr<int>(), sidx.data_ptr<int>(),
-             sval.data_ptr<float>(), fill ? 1 : 0, dp, current_stream());
+             sval.data_ptr<float>(), fill ? 1 : 0, dp, rp, n_list,
+             current_stream());
 }
 
 void sparse_fused(torch::Tensor F, torch::Tensor indptr,
@@ -481,18 +527,41 @@ void sparse_commit(torch::Tensor F, torch::Tensor order,
                    torch::Tensor best, torch::Tensor soffset,
                    torch::Tensor sidx, torch::Tensor sval,
                    torch::Tensor scount, int64_t cap, double min_f,
-                   double max_f) {
+                   double max_f, int64_t n_block, int64_t wcap,
+                   std::optional<torch::Tensor> dirty) {
+  // order[:n_block] commits one block per node (K3S), order[n_block:] one
+  // wave per node (K3W; its nodes have gcount <= wcap <= cap, so their
+  // rewritten lists fit the cap-strided slots).  n_block < 0: all K3S.
+  // dirty (uint8, indexed by row) gets 0 at every routed row.
   CHECK_F(F);
+  CHECK_IN(order, torch::kInt32);
+  CHECK_IN(goffset, torch::kInt64);
+  CHECK_IN(gidx, torch::kInt32);
+  CHECK_IN(gval, torch::kFloat32);
+  CHECK_IN(gcount, torch::kInt32);
   CHECK_IN(best, torch::kFloat32);
   CHECK_IN(soffset, torch::kInt64);
   CHECK_IN(sidx, torch::kInt32);
   CHECK_IN(sval, torch::kFloat32);
   CHECK_IN(scount, torch::kInt32);
+  const int n_total = (int)order.size(0);
+  TORCH_CHECK(goffset.size(0) >= n_total && gcount.size(0) >= n_total);
+  if (n_block < 0) n_block = n_total;
+  TORCH_CHECK(n_block <= n_total, "n_block out of range");
+  TORCH_CHECK(n_block == n_total || (wcap > 0 && wcap <= cap),
+              "wave class needs 0 < wcap <= cap");
+  unsigned char* dp = nullptr;
+  if (dirty.has_value()) {
+    TORCH_CHECK(dirty->is_cuda() && dirty->is_contiguous() &&
+                dirty->scalar_type() == torch::kUInt8 &&
+                dirty->size(0) >= F.size(0));
+    dp = dirty->data_ptr<uint8_t>();
+  }
   launch_k3s(F.data_ptr(), is_bf16(F) ? 1 : 0, order.data_ptr<int>(),
-             (int)order.size(0), i64p(goffset), gidx.data_ptr<int>(),
+             (int)n_block, n_total, i64p(goffset), gidx.data_ptr<int>(),
              gval.data_ptr<float>(), gcount.data_ptr<int>(),
              best.data_ptr<float>(), i64p(soffset), sidx.data_ptr<int>(),
-             sval.data_ptr<float>(), scount.data_ptr<int>(), (int)cap,
+             sval.data_ptr<float>(), scount.data_ptr<int>(), dp, (int)cap,
              (int)F.size(1), (float)min_f, (float)max_f, current_stream());
 }
 
@@ -686,7 +755,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linesearch", &linesearch,
         "K2: 16-candidate Armijo line search in one edge pass (CDNA4)");
   m.def("apply_step", &apply_step,
-        "K3: in-place projected commit F += s*grad (CDNA4)");
+        "K3: in-place projected commit F += s*grad (CDNA4); rows=: only "
+        "the listed rows, recording dirty[u] = steps[u] > 0",
+        py::arg("F_local"), py::arg("grad"), py::arg("steps"),
+        py::arg("min_f"), py::arg("max_f"), py::arg("rows") = py::none(),
+        py::arg("dirty") = py::none());
   m.def("conductance", &conductance,
         "K5: ego-net conductance per node (CDNA4)");
   m.def("fused_grad_ls", &fused_grad_ls,
@@ -695,7 +768,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("apply_step_colsum", &apply_step_colsum,
         "K3+colsum fused (bf16): commit F and emit per-stripe column sums");
   m.def("sparse_support", &sparse_support,
-        "KAF: per-row support compaction of F (count or fill pass)");
+        "KAF: per-row support compaction of F (count or fill pass); "
+        "rows=: only the listed rows",
+        py::arg("F"), py::arg("soffset"), py::arg("scount"), py::arg("sidx"),
+        py::arg("sval"), py::arg("cap"), py::arg("fill"), py::arg("dirty"),
+        py::arg("rows") = py::none());
   m.def("sparse_fused", &sparse_fused,
         "KFS/KFW: fused compact gradient + 16-candidate Armijo for routed "
         "nodes (LDS bitmap active sets); order[:n_block] one block per "
@@ -708,7 +785,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sparse_colsum", &sparse_colsum,
         "list-based column sums (sparse path; stale/over-cap rows dense)");
   m.def("sparse_commit", &sparse_commit,
-        "K3S: sparse projected commit confined to the active set");
+        "K3S/K3W: sparse projected commit confined to the active set; "
+        "order[:n_block] one block per node, order[n_block:] one wave per "
+        "node",
+        py::arg("F"), py::arg("order"), py::arg("goffset"), py::arg("gidx"),
+        py::arg("gval"), py::arg("gcount"), py::arg("best"),
+        py::arg("soffset"), py::arg("sidx"), py::arg("sval"),
+        py::arg("scount"), py::arg("cap"), py::arg("min_f"),
+        py::arg("max_f"), py::arg("n_block") = -1, py::arg("wcap") = 0,
+        py::arg("dirty") = py::none());
   m.def("edge_grad_llh_chunked", &edge_grad_llh_chunked,
         "K1 large-K: KD per-edge dots + KW chunked weighted accumulate");
   m.def("seed_init", &seed_init,

@@ -184,10 +184,14 @@ def apply_step(
     grad: torch.Tensor,
     steps: torch.Tensor,
     cfg: BigClamConfig,
+    rows: torch.Tensor = None,
+    dirty: torch.Tensor = None,
 ) -> None:
-    """K3: in-place projected commit on the owned rows."""
+    """K3: in-place projected commit on the owned rows.  ``rows`` (int32)
+    switches to list mode: only the listed rows are committed, one block
+    each, and ``dirty[u] = steps[u] > 0`` is recorded for them."""
     ext = ensure_loaded()
-    ext.apply_step(F_local, grad, steps, cfg.min_f, cfg.max_f)
+    ext.apply_step(F_local, grad, steps, cfg.min_f, cfg.max_f, rows, dirty)
 
 
 def apply_step_colsum(
@@ -311,14 +315,18 @@ def sparse_sweep_part(
 
 def sparse_commit(F_local: torch.Tensor, pack: dict, best: torch.Tensor,
                   state, cfg: BigClamConfig):
-    """K3S: projected commit confined to each routed node's active set,
+    """K3S/K3W: projected commit confined to each routed node's active set,
     rewriting the committed rows' persistent support lists in place (the
-    next sweep's KAF then skips them)."""
+    next sweep's KAF then skips them).  The block class
+    ``order[:n_block]`` commits one block per node, the wave class one
+    wave per node; both clear the routed rows' dirty flags."""
     ensure_loaded().sparse_commit(
         F_local, pack["order"], pack["goffset"], pack["gidx"], pack["gval"],
         pack["gcount"], best, state._sp_soffset, state._sp_sidx,
         state._sp_sval, state._sp_scount, state._sp_cap,
         cfg.min_f, cfg.max_f,
+        int(pack.get("n_block", -1)), int(pack.get("wcap", 0)),
+        state._dirty,
     )
 
 
