@@ -130,7 +130,12 @@ class ShardState:
         self._sp_soffset: Optional[torch.Tensor] = None
         self._indices64: Optional[torch.Tensor] = None
         self._order64: Optional[torch.Tensor] = None
-        self._last_nnz: Optional[torch.Tensor] = None  # from KAF scount
+        self._nnz_live = False  # _last_nnz: the KAF counts are current
+        # native routing buffers (allocated once, by the first routed
+        # sweep) and the two alternating by-class order buffers' index
+        self._rt: Optional[dict] = None
+        self._rt_flip = 0
+        self._sumF_buf: Optional[torch.Tensor] = None  # stage-2 target
         self._sp_scount: Optional[torch.Tensor] = None
         self._sp_sidx: Optional[torch.Tensor] = None
         self._sp_sval: Optional[torch.Tensor] = None
@@ -144,6 +149,7 @@ class ShardState:
         self._kaf_rows: Optional[torch.Tensor] = None
         self._side_stream = None  # hub-remainder overlap (sparse path)
         self._class_edges = None  # routing-class boundaries (device, u8)
+        self._edge_row = None  # per-edge local row (torch routing only)
         # per-edge source row (torch reference path); built lazily on CPU
         self._edge_src: Optional[torch.Tensor] = None
 
@@ -394,6 +400,93 @@ class ShardState:
 
     # ------------------------------------------------- sparse-adaptive path
     @property
+    def _last_nnz(self) -> Optional[torch.Tensor]:
+        """Support entries of the owned rows (device scalar), from the
+        persistent KAF counts; None while no sparse sweep has run.
+        Computed only when read (``fit``'s logging, the halo-compression
+        vote) — the sweep itself never needs it."""
+        if not self._nnz_live or self._sp_scount is None:
+            return None
+        return self._sp_scount[: self.n_local].sum()
+
+    @_last_nnz.setter
+    def _last_nnz(self, value):
+        assert value is None, "_last_nnz is derived; only None may be set"
+        self._nnz_live = False
+
+    @property
+    def native_route(self) -> bool:
+        """Route with the native kernels (``sparse_route``);
+        BIGCLAM_NATIVE_ROUTE=0 selects the torch routing (global prefix
+        + stable sort), the A/B switch and the tests' reference."""
+        return os.environ.get("BIGCLAM_NATIVE_ROUTE", "1") != "0"
+
+    def _route_native(self, scount, cap, wcap):
+        """One routing pass on the device: returns (epre, bound32,
+        by_class, GG, n_block, n_s).  by_class alternates between two
+        buffers so a carried pack's ``order``/``order_d`` stay valid
+        until that pack is committed and read."""
+        ext = _hip_ops().ensure_loaded()
+        rt = self._rt
+        if rt is None:
+            dev, n = self.device, self.n_local
+            tile = int(ext.sparse_route_tile())
+            nt3 = 3 * ((n + tile - 1) // tile)
+            i32 = dict(device=dev, dtype=torch.int32)
+            rt = self._rt = {
+                "epre": torch.empty(self.indices.numel(), **i32),
+                "bound": torch.empty(n, **i32),
+                "cls": torch.empty(n, device=dev, dtype=torch.uint8),
+                "tcount": torch.empty(nt3, **i32),
+                "tbase": torch.empty(nt3, **i32),
+                "totals": torch.empty(3, **i32),
+                "GG": torch.empty(1, device=dev, dtype=torch.float32),
+                "by_class": [torch.empty(n, **i32) for _ in range(2)],
+            }
+        self._rt_flip ^= 1
+        by_class = rt["by_class"][self._rt_flip]
+        n_blk, n_wave, _ = ext.sparse_route(
+            self.indptr, self.indices, scount, self.order, self.sumF,
+            cap, wcap, rt["epre"], rt["bound"], rt["cls"], rt["tcount"],
+            rt["tbase"], rt["totals"], rt["GG"], by_class,
+        )  # <- the one host sync
+        return rt["epre"], rt["bound"], by_class, rt["GG"], n_blk, \
+            n_blk + n_wave
+
+    def _route_torch(self, scount, cap, wcap):
+        """The torch routing (BIGCLAM_NATIVE_ROUTE=0): global int64
+        prefix, 3-valued key, stable sort; the kernels' node-local int32
+        prefix and saturated bound are derived from the global one."""
+        dev = self.device
+        bound, cs = self.sparse_bounds(
+            scount, self.indptr, self._indices64, self.n_local
+        )
+        key = (bound > cap).to(torch.uint8) * 2
+        if wcap > 0:
+            key += (bound <= wcap).to(torch.uint8)
+        skey, perm = torch.sort(key[self._order64], stable=True)
+        if self._class_edges is None:
+            self._class_edges = torch.tensor(
+                [1, 2], device=dev, dtype=torch.uint8
+            )
+        n_blk, n_s = torch.searchsorted(
+            skey, self._class_edges
+        ).tolist()  # <- the one host sync
+        by_class = self.order[perm]
+        if self._edge_row is None:
+            deg = self.indptr[1:] - self.indptr[:-1]
+            self._edge_row = torch.repeat_interleave(
+                torch.arange(self.n_local, device=dev), deg
+            )
+        epre = (
+            (cs[:-1] - cs[self.indptr[:-1]][self._edge_row])
+            .clamp_(max=cap + 1).to(torch.int32)
+        )
+        bound32 = bound.clamp(max=cap + 1).to(torch.int32)
+        GG = (self.sumF * self.sumF).sum().reshape(1)
+        return epre, bound32, by_class, GG, n_blk, n_s
+
+    @property
     def sparse_cap(self) -> int:
         """Active-set bound under which a node routes to the KFS sparse
         kernel.  kp/4 keeps the compact work well under the dense
@@ -609,29 +702,16 @@ class ShardState:
                 self.F, soffset, scount, sidx, sval, cap, True, dirty
             )
         self._kaf_valid = True
-        self._last_nnz = scount[: self.n_local].sum()
-        bound, cs = self.sparse_bounds(
-            scount, self.indptr, self._indices64, self.n_local
-        )
+        self._nnz_live = True
         # three classes by the exact bound: 0 = block kernel (wcap < bound
         # <= cap), 1 = wave kernel (bound <= wcap), 2 = dense remainder.
-        # A stable sort of the class key over the degree-descending launch
-        # order keeps every class degree-descending and lays the routed
-        # order out as [block | wave]; the class sizes are the sweep's one
-        # host sync.
+        # A stable placement of the class key over the degree-descending
+        # launch order keeps every class degree-descending and lays the
+        # order out as [block | wave | dense]; the class sizes are the
+        # sweep's one routing host sync.
         wcap = self.sparse_wcap
-        key = (bound > cap).to(torch.uint8) * 2
-        if wcap > 0:
-            key += (bound <= wcap).to(torch.uint8)
-        skey, perm = torch.sort(key[self._order64], stable=True)
-        if self._class_edges is None:
-            self._class_edges = torch.tensor(
-                [1, 2], device=dev, dtype=torch.uint8
-            )
-        n_blk, n_s = torch.searchsorted(
-            skey, self._class_edges
-        ).tolist()  # <- the one host sync
-        by_class = self.order[perm]
+        route = self._route_native if self.native_route else self._route_torch
+        epre, bound32, by_class, GG, n_blk, n_s = route(scount, cap, wcap)
         order_s = by_class[:n_s]
         # engage only when a real fraction of nodes routes: at low K /
         # moderate density the bound exceeds cap for most nodes and the
@@ -641,7 +721,7 @@ class ShardState:
             g, l, b = self.fused_grad_ls_overlap(None)
             return g, l, b, None
         order_d = by_class[n_s:]
-        goffset = torch.arange(n_s, device=dev, dtype=torch.int64) * cap
+        goffset = self._sp_soffset[:n_s]  # position * cap, like soffset
         n, kp = self.n_local, self.kp
         grad = torch.empty(n, kp, device=dev, dtype=torch.float32)
         llh = torch.empty(n, device=dev, dtype=torch.float64)
@@ -681,10 +761,10 @@ class ShardState:
         # hipMalloc spikes mid-fit)
         pack = ops.sparse_sweep_part(
             self.F, self.indptr, self.indices, self.sumF, order_s,
-            soffset, sidx, sval, scount, cs, goffset,
+            soffset, sidx, sval, scount, epre, bound32, goffset,
             self.n_local * cap, cap, llh, best, self.cfg,
             state_pools=(self._sp_gidx, self._sp_gval),
-            n_block=n_blk, wcap=wcap,
+            n_block=n_blk, wcap=wcap, GG=GG,
         )
         pack["n_block"] = n_blk  # order[:n_block] block class, rest wave
         pack["wcap"] = wcap
@@ -748,7 +828,14 @@ class ShardState:
                     self._sp_sval, self._sp_scount, self._dirty,
                     self._sp_cap, self._colsum_partials,
                 )
-                self.sumF = self._colsum_partials.sum(dim=0)
+                if self._sumF_buf is None:
+                    self._sumF_buf = torch.empty(
+                        self.kp, device=self.device, dtype=torch.float32
+                    )
+                ops.ensure_loaded().colsum_stage2(
+                    self._colsum_partials, self._sumF_buf
+                )
+                self.sumF = self._sumF_buf
                 comm.all_reduce_(self.sumF)
                 return
             # fallback (BIGCLAM_SPARSE_COLSUM=0): full-grid dense commit

@@ -21,6 +21,8 @@
 //   KAF/KFS/K3S         — sparse-adaptive sweep on exact active column
 //                       sets (support compaction, fused compact
 //                       grad+Armijo, sparse commit + list rewrite)
+//   KR kr_bounds/kr_scan/kr_place — sparse-sweep routing: node-local
+//                       support prefix, bounds, classes, stable order
 //   K6 k6_seed_init     — device seed-init scatter (scala:60-87)
 //   K7 k7_membership    — device community extraction (Bigclamv2:223-230)
 //   K8 k8_cover_match   — ground-truth best-match F1/Jaccard; lives in
@@ -2540,12 +2542,263 @@ __global__ void __launch_bounds__(BLOCK) kaf_support_t(
   }
 }
 
+// ---------------------------------------------------------------- routing
+//
+// Per-sweep routing of the sparse path in three launches (no global
+// prefix over the edges, no sort):
+//   kr_bounds  walks the degree-descending launch order, RT_GRP lanes per
+//              node (the whole block for a node above RT_HUB edges), and
+//              writes the NODE-LOCAL exclusive support prefix per edge
+//              (epre, int32), the per-node bound s_u + sum s_v, the class
+//              per position (0 block / 1 wave / 2 dense) and per-tile
+//              class counts;
+//   kr_scan    one block: tile counts -> per-tile bases + class totals,
+//              and GG = sum sumF^2 in a fixed order;
+//   kr_place   stable placement into [block | wave | dense]: every class
+//              keeps the launch order (what a stable sort of the 3-valued
+//              key gives).
+// All sums SATURATE at cap + 1 (scount holds the full count of an
+// over-cap row, so a hub's true bound can pass 2^31); saturating adds of
+// non-negative ints stay associative, so bound == min(true, cap + 1) and
+// epre is exact on every node with bound <= cap — the only readers.  A
+// node stops walking once it saturates (it is dense; its epre is unread).
+
+#define RT_TILE 64     // launch-order positions per tile (one wave places it)
+#define RT_GRP 16      // lanes per node in the bounds walk
+#define RT_HUB 512     // degree above which the whole block walks the node
+#define RT_SCAN 1024   // threads of the single scan block
+
+__device__ __forceinline__ int sat_add(int a, int b, int sat) {
+  return min(a + b, sat);
+}
+
+__device__ __forceinline__ int route_class(int b, int cap, int wcap) {
+  return b > cap ? 2 : ((wcap > 0 && b <= wcap) ? 1 : 0);
+}
+
+__global__ void __launch_bounds__(BLOCK) kr_bounds(
+    const long long* __restrict__ indptr, const int* __restrict__ indices,
+    const int* __restrict__ scount, const int* __restrict__ order,
+    int n_local, int cap, int wcap, int* __restrict__ epre,
+    int* __restrict__ bound, unsigned char* __restrict__ cls,
+    int* __restrict__ tcount) {
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int wid = tid >> 6;
+  const int grp = tid / RT_GRP;
+  const int gl = tid % RT_GRP;
+  const int sat = cap + 1;
+  const int p0 = blockIdx.x * RT_TILE;
+  __shared__ unsigned char s_cls[RT_TILE];
+  __shared__ int s_hub[RT_TILE];
+  __shared__ int s_nhub;
+  __shared__ int s_scan[NWAVE];
+  if (tid == 0) s_nhub = 0;
+  __syncthreads();
+  constexpr int NGRP = BLOCK / RT_GRP;
+  for (int r = 0; r < RT_TILE / NGRP; ++r) {
+    const int q = r * NGRP + grp;  // position in the tile (group-uniform)
+    if (p0 + q >= n_local) continue;
+    const int u = order[p0 + q];
+    const long long e0 = indptr[u];
+    const long long degl = indptr[u + 1] - e0;
+    if (degl > RT_HUB) {
+      if (gl == 0) s_hub[atomicAdd(&s_nhub, 1)] = q;
+      continue;
+    }
+    const int deg = (int)degl;
+    int carry = 0;
+    for (int i0 = 0; i0 < deg && carry < sat; i0 += RT_GRP) {
+      const int i = i0 + gl;
+      const int s = i < deg ? min(scount[indices[e0 + i]], sat) : 0;
+      int incl = s;
+#pragma unroll
+      for (int off = 1; off < RT_GRP; off <<= 1) {
+        const int v = __shfl_up(incl, off, RT_GRP);
+        if (gl >= off) incl = sat_add(incl, v, sat);
+      }
+      // exclusive = the lower lane's inclusive value
+      const int lo = __shfl_up(incl, 1, RT_GRP);
+      if (i < deg) epre[e0 + i] = sat_add(carry, gl ? lo : 0, sat);
+      carry = sat_add(carry, __shfl(incl, RT_GRP - 1, RT_GRP), sat);
+    }
+    if (gl == 0) {
+      const int b = sat_add(min(scount[u], sat), carry, sat);
+      bound[u] = b;
+      s_cls[q] = (unsigned char)route_class(b, cap, wcap);
+    }
+  }
+  __syncthreads();
+  // hubs: the whole block walks one node, 4 consecutive edges per thread
+  const int nh = s_nhub;
+  for (int h = 0; h < nh; ++h) {
+    const int q = s_hub[h];
+    const int u = order[p0 + q];
+    const long long e0 = indptr[u];
+    const long long deg = indptr[u + 1] - e0;
+    int carry = 0;
+    for (long long i0 = 0; i0 < deg && carry < sat; i0 += BLOCK * 4) {
+      const long long i = i0 + tid * 4;
+      int s[4];
+      int tsum = 0;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        s[t] = i + t < deg ? min(scount[indices[e0 + i + t]], sat) : 0;
+        tsum = sat_add(tsum, s[t], sat);
+      }
+      int incl = tsum;
+#pragma unroll
+      for (int off = 1; off < WAVE; off <<= 1) {
+        const int v = __shfl_up(incl, off, WAVE);
+        if (lane >= off) incl = sat_add(incl, v, sat);
+      }
+      __syncthreads();  // the previous round's s_scan reads are done
+      if (lane == WAVE - 1) s_scan[wid] = incl;
+      __syncthreads();
+      int run = carry, total = 0;
+#pragma unroll
+      for (int wv = 0; wv < NWAVE; ++wv) {
+        if (wv < wid) run = sat_add(run, s_scan[wv], sat);
+        total = sat_add(total, s_scan[wv], sat);
+      }
+      const int lo = __shfl_up(incl, 1, WAVE);
+      run = sat_add(run, lane ? lo : 0, sat);
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        if (i + t < deg) {
+          epre[e0 + i + t] = run;
+          run = sat_add(run, s[t], sat);
+        }
+      carry = sat_add(carry, total, sat);
+    }
+    if (tid == 0) {
+      const int b = sat_add(min(scount[u], sat), carry, sat);
+      bound[u] = b;
+      s_cls[q] = (unsigned char)route_class(b, cap, wcap);
+    }
+  }
+  __syncthreads();
+  if (wid == 0) {  // RT_TILE == WAVE: one lane per position
+    const int p = p0 + lane;
+    const int c = p < n_local ? (int)s_cls[lane] : 3;
+    if (p < n_local) cls[p] = (unsigned char)c;
+    const unsigned long long m0 = __ballot(c == 0);
+    const unsigned long long m1 = __ballot(c == 1);
+    const unsigned long long m2 = __ballot(c == 2);
+    if (lane < 3)
+      tcount[blockIdx.x * 3 + lane] =
+          __popcll(lane == 0 ? m0 : (lane == 1 ? m1 : m2));
+  }
+}
+
+// tile counts -> exclusive per-class tile bases + the three totals; GG
+__global__ void __launch_bounds__(RT_SCAN) kr_scan(
+    const int* __restrict__ tcount, int n_tiles, int* __restrict__ tbase,
+    int* __restrict__ totals, const float* __restrict__ sumF, int K,
+    float* __restrict__ GG) {
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int wid = tid >> 6;
+  constexpr int NW = RT_SCAN / WAVE;
+  __shared__ int s_w[NW][3];
+  __shared__ float s_g[NW];
+  const int chunk = (n_tiles + RT_SCAN - 1) / RT_SCAN;
+  const int t0 = min(tid * chunk, n_tiles);
+  const int t1 = min(t0 + chunk, n_tiles);
+  int c[3] = {0, 0, 0};
+  for (int t = t0; t < t1; ++t) {
+    c[0] += tcount[t * 3];
+    c[1] += tcount[t * 3 + 1];
+    c[2] += tcount[t * 3 + 2];
+  }
+  int incl[3] = {c[0], c[1], c[2]};
+#pragma unroll
+  for (int off = 1; off < WAVE; off <<= 1) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int v = __shfl_up(incl[j], off, WAVE);
+      if (lane >= off) incl[j] += v;
+    }
+  }
+  // GG in a fixed order: strided per-thread sums, xor tree, waves in order
+  float g = 0.f;
+  for (int k = tid; k < K; k += RT_SCAN) g = fmaf(sumF[k], sumF[k], g);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) g += __shfl_xor(g, off, WAVE);
+  if (lane == WAVE - 1) {
+    s_w[wid][0] = incl[0];
+    s_w[wid][1] = incl[1];
+    s_w[wid][2] = incl[2];
+    s_g[wid] = g;
+  }
+  __syncthreads();
+  int run[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    int b = 0;
+    for (int wv = 0; wv < wid; ++wv) b += s_w[wv][j];
+    run[j] = b + incl[j] - c[j];
+  }
+  for (int t = t0; t < t1; ++t) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      tbase[t * 3 + j] = run[j];
+      run[j] += tcount[t * 3 + j];
+    }
+  }
+  if (tid == 0) {
+    float gs = 0.f;
+    int tot[3] = {0, 0, 0};
+    for (int wv = 0; wv < NW; ++wv) {
+      gs += s_g[wv];
+      tot[0] += s_w[wv][0];
+      tot[1] += s_w[wv][1];
+      tot[2] += s_w[wv][2];
+    }
+    GG[0] = gs;
+    totals[0] = tot[0];
+    totals[1] = tot[1];
+    totals[2] = tot[2];
+  }
+}
+
+// stable placement: one wave per tile, rank inside the tile by ballot
+__global__ void __launch_bounds__(BLOCK) kr_place(
+    const int* __restrict__ order, const unsigned char* __restrict__ cls,
+    const int* __restrict__ tbase, const int* __restrict__ totals,
+    int n_local, int n_tiles, int* __restrict__ by_class) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int tile = blockIdx.x * NWAVE + (threadIdx.x >> 6);
+  if (tile >= n_tiles) return;  // wave-uniform
+  const int p = tile * RT_TILE + lane;
+  const int c = p < n_local ? (int)cls[p] : 3;
+  const unsigned long long m0 = __ballot(c == 0);
+  const unsigned long long m1 = __ballot(c == 1);
+  const unsigned long long m2 = __ballot(c == 2);
+  if (c < 3) {
+    const unsigned long long m = c == 0 ? m0 : (c == 1 ? m1 : m2);
+    const int rank = __popcll(m & ((1ull << lane) - 1ull));
+    const int cbase =
+        (c >= 1 ? totals[0] : 0) + (c == 2 ? totals[1] : 0);
+    by_class[cbase + tbase[tile * 3 + c] + rank] = order[p];
+  }
+}
+
+// One edge's staged list length from the node-local prefix: up to the
+// next edge's base, or to the node's staged total (bound - own support)
+// at the last edge.
+__device__ __forceinline__ int epre_len(const int* __restrict__ epre,
+                                        long long e, int i, int deg,
+                                        int total) {
+  return (i + 1 < deg ? epre[e + 1] : total) - epre[e];
+}
+
 // KFS: the fused sparse sweep — ONE launch per sweep for the routed
 // nodes.  Evolution is measured in profiles/r02_sparse_sweep.md; the
 // current (v10) structure:
 //   * ALL neighbor-list entries staged in LDS once (<= cap by routing;
-//     per-edge bases come FREE from the host's epos prefix — the same
-//     cumsum grad_ls_auto builds for the routing bounds);
+//     per-edge bases come from the routing pass's node-local int32
+//     prefix epre, the staged total from its bound);
 //   * the active set S_u = supp(gacc) ∪ supp(fu) is built FIRST from an
 //     LDS bitmap (phase 1 ORs bits while staging), so the accumulator
 //     gacc is COMPACT (cap slots, not K): no O(K) LDS residency, no
@@ -2580,7 +2833,8 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
     const float* __restrict__ sumF, const int* __restrict__ order,
     const long long* __restrict__ soffset, const int* __restrict__ sidx,
     const float* __restrict__ sval, const int* __restrict__ scount,
-    const long long* __restrict__ epos, const long long* __restrict__ goffset,
+    const int* __restrict__ epre, const int* __restrict__ bound,
+    const long long* __restrict__ goffset,
     int* __restrict__ gidx, float* __restrict__ gval,
     int* __restrict__ gcount, double* __restrict__ llh,
     const float* __restrict__ GGp, const float* __restrict__ ladder,
@@ -2626,13 +2880,14 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
   __syncthreads();
 
   // phase 1: stage neighbor lists (wave-per-edge) + OR support bits
-  const long long p0 = epos[e0];
+  const int deg = (int)(e1 - e0);
+  const int total = bound[u] - scount[u];  // staged entries
   if (phases & 8)
   for (long long e = e0 + wid; e < e1; e += NWAVE) {
     const int v = indices[e];
     const long long off = soffset[v];
     const int sv = scount[v];
-    const int base = (int)(epos[e] - p0);
+    const int base = epre[e];
     for (int j = lane; j < sv; j += WAVE) {
       const int k = sidx[off + j];
       nidx[base + j] = (unsigned short)k;
@@ -2693,7 +2948,6 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
   }
   __syncthreads();
   {  // staged column ids -> compact positions, in place
-    const int total = (int)(epos[e1] - p0);
     for (int i = tid; i < total; i += BLOCK) {
       const int k = (int)nidx[i];  // always present: k came from bmap
       const int wv = k >> 5;
@@ -2708,8 +2962,8 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
   double llh_acc = 0.0;
   if (phases & 1)
   for (long long e = e0 + wid; e < e1; e += NWAVE) {
-    const int base = (int)(epos[e] - p0);
-    const int sv = (int)(epos[e + 1] - epos[e]);
+    const int base = epre[e];
+    const int sv = epre_len(epre, e, (int)(e - e0), deg, total);
     float part = 0.f;
     for (int j = lane; j < sv; j += WAVE) {
       const int p_ = (int)nidx[base + j];
@@ -2788,8 +3042,8 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
       const int ne = (int)min((long long)16, e1 - et);
       if (ej < ne && jc < n_ladder) {
         const long long e = et + ej;
-        const int base = (int)(epos[e] - p0);
-        const int sv = (int)(epos[e + 1] - epos[e]);
+        const int base = epre[e];
+        const int sv = epre_len(epre, e, (int)(e - e0), deg, total);
         float x = 0.f;
         for (int t = 0; t < sv; ++t) {
           const int p_ = (int)nidx[base + t];
@@ -2844,9 +3098,9 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
 // has no cross-wave synchronisation at all (__syncthreads() is only an
 // LDS wait here) and a CU holds 4x as many nodes in flight.  Differences
 // from KFS, same formulas / fp32-fp64 split / clamps otherwise:
-//   * per-edge (base, count) pairs are computed once from epos and kept
+//   * per-edge (base, count) pairs are computed once from epre and kept
 //     in LDS (first KFW_ECAP edges; later edges of a rare wide node
-//     re-read epos) — no int64 epos reads inside the phase loops;
+//     re-read epre) — no prefix reads inside the phase loops;
 //   * staged column -> slot by RANK: per-word exclusive prefix + popcount
 //     of the lower bits (two LDS reads, no binary search);
 //   * own row values come from the node's support list (contiguous)
@@ -2872,7 +3126,8 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
     const int* __restrict__ order, int blk0,
     const long long* __restrict__ soffset, const int* __restrict__ sidx,
     const float* __restrict__ sval, const int* __restrict__ scount,
-    const long long* __restrict__ epos, const long long* __restrict__ goffset,
+    const int* __restrict__ epre, const int* __restrict__ bound,
+    const long long* __restrict__ goffset,
     int* __restrict__ gidx, float* __restrict__ gval,
     int* __restrict__ gcount, double* __restrict__ llh,
     const float* __restrict__ GGp, const float* __restrict__ ladder,
@@ -2903,18 +3158,18 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
   unsigned short* nval_h = pref + ((nw + 1) & ~1);
   unsigned short* fuS_h = nval_h + wcap;
 
-  // edge table: (staging base << 16) | list length, from the epos prefix
-  const long long p0 = epos[e0];
-  if (lane < deg) {  // KFW_ECAP == WAVE: one pass
-    const long long a = epos[e0 + lane];
-    ebs[lane] = ((u32)(a - p0) << 16) | (u32)(epos[e0 + lane + 1] - a);
-  }
+  // edge table: (staging base << 16) | list length, from the node-local
+  // prefix
+  const int total = bound[u] - scount[u];  // staged entries
+  if (lane < deg)  // KFW_ECAP == WAVE: one pass
+    ebs[lane] = ((u32)epre[e0 + lane] << 16) |
+                (u32)epre_len(epre, e0 + lane, lane, deg, total);
   for (int i = lane; i < nw; i += WAVE) bmap[i] = 0u;
   __syncthreads();
   auto edge_bs = [&](int i) -> u32 {
     if (i < KFW_ECAP) return ebs[i];
-    const long long a = epos[e0 + i];
-    return ((u32)(a - p0) << 16) | (u32)(epos[e0 + i + 1] - a);
+    return ((u32)epre[e0 + i] << 16) |
+           (u32)epre_len(epre, e0 + i, i, deg, total);
   };
 
   // phase 1: stage neighbour lists, 4 edges at a time (16 lanes per
@@ -2993,7 +3248,6 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
       fuS_f[p_] = sval[offu + j];
   }
   {  // staged column ids -> slot positions, in place
-    const int total = (int)(epos[e0 + deg] - p0);
     for (int i = lane; i < total; i += WAVE)
       nidx[i] = (unsigned short)rank_of((int)nidx[i]);
   }
@@ -3261,7 +3515,7 @@ __global__ void __launch_bounds__(BLOCK) k3w_commit_t(
 // and rows the DENSE path just committed (dirty) — read their F row
 // directly, so the result is exact for the current F.  Per-stripe fp32
 // partials land in the same [n_stripes, K] buffer as k3_colsum_bf16;
-// stage 2 (partials.sum(0)) stays deterministic.  Within a block the
+// stage 2 (kcs_stage2) sums them in a fixed order.  Within a block the
 // list entries accumulate via LDS atomics — the same run-to-run fp-order
 // trade the sparse gradient already makes (the dense path keeps the
 // bitwise-deterministic k3_colsum).
@@ -3310,6 +3564,46 @@ __global__ void __launch_bounds__(BLOCK) kcs_lists_t(
   for (int k = tid * 4; k < cw; k += BLOCK * 4)
     *reinterpret_cast<float4*>(out + k) =
         *reinterpret_cast<const float4*>(acc + k);
+}
+
+// Stage 2 of the list-based refresh: out[k] = sum over stripes of
+// partials[s, k], in an order fixed by KCS2_RG alone (never by the launch
+// geometry): stripe s goes to row group s % KCS2_RG, every group adds its
+// stripes in ascending order, and the groups combine in ascending order.
+// One float4 of columns per lane, 8 lanes = 128 B of a row per group.
+#define KCS2_RG 32
+
+__global__ void __launch_bounds__(BLOCK) kcs_stage2(
+    const float* __restrict__ partials, int ns, int K,
+    float* __restrict__ out) {
+  constexpr int CL = BLOCK / KCS2_RG;  // column lanes per group
+  const int cl = threadIdx.x % CL;
+  const int rg = threadIdx.x / CL;
+  const int k = (blockIdx.x * CL + cl) * 4;
+  __shared__ float4 red[KCS2_RG][CL];
+  float4 acc = float4{0.f, 0.f, 0.f, 0.f};
+  if (k < K) {
+#pragma unroll 4
+    for (int s = rg; s < ns; s += KCS2_RG) {
+      const float4 v = ld4(partials + (size_t)s * K + k);
+      acc.x += v.x;
+      acc.y += v.y;
+      acc.z += v.z;
+      acc.w += v.w;
+    }
+  }
+  red[rg][cl] = acc;
+  __syncthreads();
+  if (threadIdx.x < CL && k < K) {
+    float4 t = red[0][cl];
+    for (int j = 1; j < KCS2_RG; ++j) {
+      t.x += red[j][cl].x;
+      t.y += red[j][cl].y;
+      t.z += red[j][cl].z;
+      t.w += red[j][cl].w;
+    }
+    *reinterpret_cast<float4*>(out + k) = t;
+  }
 }
 
 // ------------------------------------------------------------------- K6
@@ -3873,7 +4167,8 @@ extern "C" void launch_kfs(const void* F, int bf16,
                            const float* sumF, const int* order, int n_blocks,
                            const long long* soffset, const int* sidx,
                            const float* sval, const int* scount,
-                           const long long* epos, const long long* goffset,
+                           const int* epre, const int* bound,
+                           const long long* goffset,
                            int* gidx, float* gval, int* gcount, double* llh,
                            const float* GGp, const float* ladder,
                            float* best, int n_ladder, int cap, int K,
@@ -3889,14 +4184,14 @@ extern "C" void launch_kfs(const void* F, int bf16,
     allow_large_lds((const void*)&kfs_sparse_t<true>, lds);
     hipLaunchKernelGGL((kfs_sparse_t<true>), dim3(n_blocks), dim3(BLOCK),
                        lds, stream, F, K, indptr, indices, sumF, order,
-                       soffset, sidx, sval, scount, epos, goffset, gidx,
+                       soffset, sidx, sval, scount, epre, bound, goffset, gidx,
                        gval, gcount, llh, GGp, ladder, best, n_ladder, cap,
                        alpha, min_p, max_p, min_f, max_f, phases);
   } else {
     allow_large_lds((const void*)&kfs_sparse_t<false>, lds);
     hipLaunchKernelGGL((kfs_sparse_t<false>), dim3(n_blocks), dim3(BLOCK),
                        lds, stream, F, K, indptr, indices, sumF, order,
-                       soffset, sidx, sval, scount, epos, goffset, gidx,
+                       soffset, sidx, sval, scount, epre, bound, goffset, gidx,
                        gval, gcount, llh, GGp, ladder, best, n_ladder, cap,
                        alpha, min_p, max_p, min_f, max_f, phases);
   }
@@ -3916,7 +4211,8 @@ extern "C" void launch_kfw(int bf16, const long long* indptr,
                            const int* order, int blk0, int n_blocks,
                            const long long* soffset, const int* sidx,
                            const float* sval, const int* scount,
-                           const long long* epos, const long long* goffset,
+                           const int* epre, const int* bound,
+                           const long long* goffset,
                            int* gidx, float* gval, int* gcount, double* llh,
                            const float* GGp, const float* ladder,
                            float* best, int n_ladder, int wcap, int K,
@@ -3931,14 +4227,14 @@ extern "C" void launch_kfw(int bf16, const long long* indptr,
     allow_large_lds((const void*)&kfw_sparse_t<true>, lds);
     hipLaunchKernelGGL((kfw_sparse_t<true>), dim3(n_blocks), dim3(WAVE), lds,
                        stream, K, indptr, indices, sumF, order, blk0,
-                       soffset, sidx, sval, scount, epos, goffset, gidx,
+                       soffset, sidx, sval, scount, epre, bound, goffset, gidx,
                        gval, gcount, llh, GGp, ladder, best, n_ladder, wcap,
                        alpha, min_p, max_p, min_f, max_f);
   } else {
     allow_large_lds((const void*)&kfw_sparse_t<false>, lds);
     hipLaunchKernelGGL((kfw_sparse_t<false>), dim3(n_blocks), dim3(WAVE), lds,
                        stream, K, indptr, indices, sumF, order, blk0,
-                       soffset, sidx, sval, scount, epos, goffset, gidx,
+                       soffset, sidx, sval, scount, epre, bound, goffset, gidx,
                        gval, gcount, llh, GGp, ladder, best, n_ladder, wcap,
                        alpha, min_p, max_p, min_f, max_f);
   }
@@ -4019,6 +4315,43 @@ extern "C" void launch_kcs_lists(const void* F, int bf16, int n_local,
                        stream, F, n_local, K, soffset, sidx, sval, scount,
                        dirty, cap, partials);
   }
+  HIP_CHECK(hipGetLastError());
+}
+
+extern "C" void launch_kcs_stage2(const float* partials, int ns, int K,
+                                  float* out, hipStream_t stream) {
+  if (K == 0) return;
+  const int cols = (BLOCK / KCS2_RG) * 4;  // columns per block
+  hipLaunchKernelGGL(kcs_stage2, dim3((K + cols - 1) / cols), dim3(BLOCK), 0,
+                     stream, partials, ns, K, out);
+  HIP_CHECK(hipGetLastError());
+}
+
+extern "C" int route_tile() { return RT_TILE; }
+
+// Routing: bounds + classes, tile scan (+ GG), stable placement.  The
+// three class totals are left in `totals` (device) for the caller's one
+// host read.  tcount/tbase hold 3 ints per tile.
+extern "C" void launch_route(const long long* indptr, const int* indices,
+                             const int* scount, const int* order,
+                             int n_local, int cap, int wcap,
+                             const float* sumF, int K, int* epre, int* bound,
+                             unsigned char* cls, int* tcount, int* tbase,
+                             int* totals, float* GG, int* by_class,
+                             hipStream_t stream) {
+  static_assert(RT_TILE == WAVE && RT_TILE % (BLOCK / RT_GRP) == 0,
+                "one wave places a tile; groups cover it in whole rounds");
+  const int n_tiles = (n_local + RT_TILE - 1) / RT_TILE;
+  if (n_tiles > 0)
+    hipLaunchKernelGGL(kr_bounds, dim3(n_tiles), dim3(BLOCK), 0, stream,
+                       indptr, indices, scount, order, n_local, cap, wcap,
+                       epre, bound, cls, tcount);
+  hipLaunchKernelGGL(kr_scan, dim3(1), dim3(RT_SCAN), 0, stream, tcount,
+                     n_tiles, tbase, totals, sumF, K, GG);
+  if (n_tiles > 0)
+    hipLaunchKernelGGL(kr_place, dim3((n_tiles + NWAVE - 1) / NWAVE),
+                       dim3(BLOCK), 0, stream, order, cls, tbase, totals,
+                       n_local, n_tiles, by_class);
   HIP_CHECK(hipGetLastError());
 }
 

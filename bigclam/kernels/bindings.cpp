@@ -392,15 +392,15 @@ extern "C" void launch_kaf(const void*, int, int, int, int,
 extern "C" void launch_kfs(const void*, int, const long long*, const int*,
                            const float*, const int*, int, const long long*,
                            const int*, const float*, const int*,
-                           const long long*, const long long*, int*, float*,
-                           int*, double*, const float*, const float*,
+                           const int*, const int*, const long long*, int*,
+                           float*, int*, double*, const float*, const float*,
                            float*, int, int, int, float, float, float,
                            float, float, hipStream_t);
 extern "C" void launch_kfw(int, const long long*, const int*, const float*,
                            const int*, int, int, const long long*,
                            const int*, const float*, const int*,
-                           const long long*, const long long*, int*, float*,
-                           int*, double*, const float*, const float*,
+                           const int*, const int*, const long long*, int*,
+                           float*, int*, double*, const float*, const float*,
                            float*, int, int, int, float, float, float,
                            float, float, hipStream_t);
 extern "C" long long kfw_lds_bytes(int, int, int);
@@ -456,8 +456,8 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
                   torch::Tensor indices, torch::Tensor sumF,
                   torch::Tensor order, torch::Tensor soffset,
                   torch::Tensor sidx, torch::Tensor sval,
-                  torch::Tensor scount, torch::Tensor epos,
-                  torch::Tensor goffset, torch::Tensor gidx,
+                  torch::Tensor scount, torch::Tensor epre,
+                  torch::Tensor bound, torch::Tensor goffset, torch::Tensor gidx,
                   torch::Tensor gval, torch::Tensor gcount,
                   torch::Tensor llh, torch::Tensor GG, torch::Tensor ladder,
                   torch::Tensor best, int64_t cap, double alpha,
@@ -475,7 +475,8 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
   CHECK_IN(sidx, torch::kInt32);
   CHECK_IN(sval, torch::kFloat32);
   CHECK_IN(scount, torch::kInt32);
-  CHECK_IN(epos, torch::kInt64);
+  CHECK_IN(epre, torch::kInt32);
+  CHECK_IN(bound, torch::kInt32);
   CHECK_IN(goffset, torch::kInt64);
   CHECK_IN(gidx, torch::kInt32);
   CHECK_IN(gval, torch::kFloat32);
@@ -486,7 +487,8 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
   CHECK_IN(best, torch::kFloat32);
   const int n_blocks = (int)order.size(0);
   TORCH_CHECK(goffset.size(0) >= n_blocks && gcount.size(0) >= n_blocks);
-  TORCH_CHECK(epos.size(0) == indices.size(0) + 1, "epos must be nnz+1");
+  TORCH_CHECK(epre.size(0) == indices.size(0), "epre must be [nnz]");
+  TORCH_CHECK(bound.size(0) + 1 == indptr.size(0), "bound must be [n_local]");
   TORCH_CHECK(n_block >= 0 && n_block <= n_blocks, "n_block out of range");
   const int n_wave = n_blocks - (int)n_block;
   TORCH_CHECK(n_wave == 0 || (wcap > 0 && wcap <= cap),
@@ -497,7 +499,8 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
                indices.data_ptr<int>(), sumF.data_ptr<float>(),
                order.data_ptr<int>(), (int)n_block, n_wave, i64p(soffset),
                sidx.data_ptr<int>(), sval.data_ptr<float>(),
-               scount.data_ptr<int>(), i64p(epos), i64p(goffset),
+               scount.data_ptr<int>(), epre.data_ptr<int>(),
+               bound.data_ptr<int>(), i64p(goffset),
                gidx.data_ptr<int>(), gval.data_ptr<float>(),
                gcount.data_ptr<int>(), llh.data_ptr<double>(),
                GG.data_ptr<float>(), ladder.data_ptr<float>(),
@@ -511,7 +514,7 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
              reinterpret_cast<const long long*>(soffset.data_ptr<int64_t>()),
              sidx.data_ptr<int>(), sval.data_ptr<float>(),
              scount.data_ptr<int>(),
-             reinterpret_cast<const long long*>(epos.data_ptr<int64_t>()),
+             epre.data_ptr<int>(), bound.data_ptr<int>(),
              reinterpret_cast<const long long*>(goffset.data_ptr<int64_t>()),
              gidx.data_ptr<int>(), gval.data_ptr<float>(),
              gcount.data_ptr<int>(), llh.data_ptr<double>(),
@@ -607,6 +610,75 @@ void sparse_colsum(torch::Tensor F_local, torch::Tensor soffset,
                    sval.data_ptr<float>(), scount.data_ptr<int>(),
                    dirty.data_ptr<uint8_t>(), (int)cap,
                    partials.data_ptr<float>(), current_stream());
+}
+
+extern "C" void launch_kcs_stage2(const float*, int, int, float*,
+                                  hipStream_t);
+extern "C" int route_tile();
+extern "C" void launch_route(const long long*, const int*, const int*,
+                             const int*, int, int, int, const float*, int,
+                             int*, int*, unsigned char*, int*, int*, int*,
+                             float*, int*, hipStream_t);
+
+// Stage 2 of the column-sum refresh: out[k] = sum_s partials[s, k] in a
+// fixed order (see kcs_stage2).
+void colsum_stage2(torch::Tensor partials, torch::Tensor out) {
+  CHECK_IN(partials, torch::kFloat32);
+  CHECK_IN(out, torch::kFloat32);
+  TORCH_CHECK(partials.dim() == 2 && out.dim() == 1 &&
+              out.size(0) == partials.size(1));
+  TORCH_CHECK(partials.size(1) % 4 == 0, "K must be a multiple of 4");
+  launch_kcs_stage2(partials.data_ptr<float>(), (int)partials.size(0),
+                    (int)partials.size(1), out.data_ptr<float>(),
+                    current_stream());
+}
+
+// Sparse-path routing (kr_bounds / kr_scan / kr_place): fills epre
+// [nnz], bound [n_local], by_class [n_local] = [block | wave | dense] and
+// GG [1]; returns the three class sizes (the sweep's routing host sync).
+// cls/tcount/tbase/totals are scratch the caller keeps allocated.
+std::vector<int64_t> sparse_route(
+    torch::Tensor indptr, torch::Tensor indices, torch::Tensor scount,
+    torch::Tensor order, torch::Tensor sumF, int64_t cap, int64_t wcap,
+    torch::Tensor epre, torch::Tensor bound, torch::Tensor cls,
+    torch::Tensor tcount, torch::Tensor tbase, torch::Tensor totals,
+    torch::Tensor GG, torch::Tensor by_class) {
+  CHECK_IN(indptr, torch::kInt64);
+  CHECK_IN(indices, torch::kInt32);
+  CHECK_IN(scount, torch::kInt32);
+  CHECK_IN(order, torch::kInt32);
+  CHECK_IN(sumF, torch::kFloat32);
+  CHECK_IN(epre, torch::kInt32);
+  CHECK_IN(bound, torch::kInt32);
+  CHECK_IN(cls, torch::kUInt8);
+  CHECK_IN(tcount, torch::kInt32);
+  CHECK_IN(tbase, torch::kInt32);
+  CHECK_IN(totals, torch::kInt32);
+  CHECK_IN(GG, torch::kFloat32);
+  CHECK_IN(by_class, torch::kInt32);
+  const int64_t n_local = order.size(0);
+  const int64_t n_tiles = (n_local + route_tile() - 1) / route_tile();
+  TORCH_CHECK(indptr.size(0) == n_local + 1 && scount.size(0) >= n_local);
+  TORCH_CHECK(epre.size(0) == indices.size(0), "epre must be [nnz]");
+  TORCH_CHECK(bound.size(0) == n_local && cls.size(0) == n_local &&
+              by_class.size(0) == n_local);
+  TORCH_CHECK(tcount.size(0) >= 3 * n_tiles && tbase.size(0) >= 3 * n_tiles &&
+              totals.size(0) >= 3 && GG.size(0) >= 1);
+  TORCH_CHECK(cap >= 0 && cap < (1 << 29) && wcap >= 0 && wcap <= cap,
+              "need 0 <= wcap <= cap < 2^29");
+  hipStream_t stream = current_stream();
+  launch_route(i64p(indptr), indices.data_ptr<int>(), scount.data_ptr<int>(),
+               order.data_ptr<int>(), (int)n_local, (int)cap, (int)wcap,
+               sumF.data_ptr<float>(), (int)sumF.size(0),
+               epre.data_ptr<int>(), bound.data_ptr<int>(),
+               cls.data_ptr<uint8_t>(), tcount.data_ptr<int>(),
+               tbase.data_ptr<int>(), totals.data_ptr<int>(),
+               GG.data_ptr<float>(), by_class.data_ptr<int>(), stream);
+  int h[3] = {0, 0, 0};
+  TORCH_CHECK(hipMemcpyAsync(h, totals.data_ptr<int>(), sizeof(h),
+                             hipMemcpyDeviceToHost, stream) == hipSuccess);
+  TORCH_CHECK(hipStreamSynchronize(stream) == hipSuccess);
+  return {h[0], h[1], h[2]};
 }
 
 // K7 community extraction: two deterministic passes (count, then fill
@@ -784,6 +856,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "KFW dynamic LDS bytes at (dtype, padded K, wcap)");
   m.def("sparse_colsum", &sparse_colsum,
         "list-based column sums (sparse path; stale/over-cap rows dense)");
+  m.def("colsum_stage2", &colsum_stage2,
+        "fixed-order sum of the [n_stripes, K] column partials into out[K]");
+  m.def("sparse_route", &sparse_route,
+        "routing: node-local support prefix, bounds, classes and the stable "
+        "[block | wave | dense] order; returns the three class sizes");
+  m.def("sparse_route_tile", []() { return (int64_t)route_tile(); },
+        "launch-order positions per routing tile");
   m.def("sparse_commit", &sparse_commit,
         "K3S/K3W: sparse projected commit confined to the active set; "
         "order[:n_block] one block per node, order[n_block:] one wave per "

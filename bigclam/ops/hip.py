@@ -269,7 +269,8 @@ def sparse_sweep_part(
     sidx: torch.Tensor,
     sval: torch.Tensor,
     scount: torch.Tensor,
-    epos: torch.Tensor,
+    epre: torch.Tensor,
+    bound: torch.Tensor,
     goffset: torch.Tensor,
     gpool_size: int,  # kept for API stability; pools come from the state
     cap: int,
@@ -279,6 +280,7 @@ def sparse_sweep_part(
     state_pools=None,
     n_block: int = None,
     wcap: int = 0,
+    GG: torch.Tensor = None,
 ):
     """KFS/KFW for the routed (sparse) nodes: the compact gradient pools,
     llh per node, and the Armijo best step.  ``order_sparse[:n_block]``
@@ -286,7 +288,10 @@ def sparse_sweep_part(
     wcap) one wave per node; ``n_block=None`` sends every node to the
     block kernel.  Pools, goffset and gcount are indexed by position in
     ``order_sparse`` for both.  Writes llh_out/best_out at the routed
-    node positions; returns the commit pack for K3S."""
+    node positions; returns the commit pack for K3S.  ``epre`` (int32
+    [nnz], node-local exclusive support prefix) and ``bound`` (int32
+    [n_local]) come from the routing pass, as does ``GG`` = Σ sumF²
+    (computed here when not given)."""
     ext = ensure_loaded()
     dev = F.device
     n_s = int(order_sparse.numel())
@@ -297,10 +302,11 @@ def sparse_sweep_part(
     # module pool could be clobbered by another coexisting state
     gidx, gval = state_pools
     gcount = torch.empty(n_s, device=dev, dtype=torch.int32)
-    GG = (sumF * sumF).sum().reshape(1)  # device scalar: no host sync
+    if GG is None:
+        GG = (sumF * sumF).sum().reshape(1)  # device scalar: no host sync
     ext.sparse_fused(
         F, indptr, indices, sumF, order_sparse, soffset, sidx, sval, scount,
-        epos, goffset, gidx, gval, gcount, llh_out, GG, _ladder(cfg, dev),
+        epre, bound, goffset, gidx, gval, gcount, llh_out, GG, _ladder(cfg, dev),
         best_out, cap, cfg.alpha, cfg.min_p, cfg.max_p, cfg.min_f, cfg.max_f,
         int(n_block), int(wcap),
     )
