@@ -577,9 +577,22 @@ void seed_init(torch::Tensor F_local, torch::Tensor sindptr,
   CHECK_IN(sindptr, torch::kInt64);
   CHECK_IN(snbrs, torch::kInt64);
   CHECK_IN(seeds, torch::kInt64);
+  TORCH_CHECK(F_local.dim() == 2, "F_local must be [n_local, kp]");
+  TORCH_CHECK(sindptr.dim() == 1 && snbrs.dim() == 1 && seeds.dim() == 1,
+              "sindptr, snbrs and seeds must be 1-D");
   const int n_seeds = (int)seeds.size(0);
+  // column c = seed c: past the row width the scatter would run into the
+  // next row, and past the buffer on the last one
+  TORCH_CHECK(seeds.size(0) <= F_local.size(1), "n_seeds (", seeds.size(0),
+              ") exceeds the F_local width (", F_local.size(1), ")");
   TORCH_CHECK(sindptr.size(0) == n_seeds + 1);
+  TORCH_CHECK(start <= stop, "start (", start, ") must be <= stop (", stop,
+              ")");
   TORCH_CHECK(stop - start == F_local.size(0));
+  // one host read; init runs once per fit
+  const int64_t n_nbrs = sindptr[n_seeds].item<int64_t>();
+  TORCH_CHECK(n_nbrs == snbrs.size(0), "sindptr[-1] (", n_nbrs,
+              ") must equal the length of snbrs (", snbrs.size(0), ")");
   launch_k6(F_local.data_ptr(), is_bf16(F_local) ? 1 : 0,
             (int)F_local.size(1),
             reinterpret_cast<const long long*>(sindptr.data_ptr<int64_t>()),
@@ -687,8 +700,13 @@ void extract_count(torch::Tensor F_local, int64_t k_true, double delta,
                    torch::Tensor counts) {
   CHECK_F(F_local);
   CHECK_IN(counts, torch::kInt32);
+  TORCH_CHECK(F_local.dim() == 2, "F_local must be [n, ldF]");
+  TORCH_CHECK(counts.dim() == 1, "counts must be 1-D");
   const int n = (int)F_local.size(0);
   const int ldF = (int)F_local.size(1);
+  // the bf16 kernel reads rows as 32-bit words
+  TORCH_CHECK(!is_bf16(F_local) || ldF % 2 == 0,
+              "ldF must be even for bf16, got ", ldF);
   TORCH_CHECK(counts.size(0) == n);
   TORCH_CHECK(k_true >= 1 && k_true <= ldF, "bad k_true");
   launch_k7_count(F_local.data_ptr(), is_bf16(F_local) ? 1 : 0, n,
@@ -701,8 +719,12 @@ void extract_fill(torch::Tensor F_local, int64_t k_true, double delta,
   CHECK_F(F_local);
   CHECK_IN(offsets, torch::kInt64);
   CHECK_IN(comms, torch::kInt32);
+  TORCH_CHECK(F_local.dim() == 2, "F_local must be [n, ldF]");
+  TORCH_CHECK(offsets.dim() == 1, "offsets must be 1-D");
   const int n = (int)F_local.size(0);
   const int ldF = (int)F_local.size(1);
+  TORCH_CHECK(!is_bf16(F_local) || ldF % 2 == 0,
+              "ldF must be even for bf16, got ", ldF);
   TORCH_CHECK(offsets.size(0) == n);
   TORCH_CHECK(k_true >= 1 && k_true <= ldF, "bad k_true");
   launch_k7_fill(F_local.data_ptr(), is_bf16(F_local) ? 1 : 0, n,
@@ -811,6 +833,9 @@ void conductance(torch::Tensor indptr, torch::Tensor indices,
   CHECK_IN(indptr, torch::kInt64);
   CHECK_IN(indices, torch::kInt32);
   CHECK_IN(cond, torch::kFloat64);
+  TORCH_CHECK(indptr.dim() == 1 && indptr.size(0) >= 1,
+              "indptr must be 1-D and non-empty ([N+1])");
+  TORCH_CHECK(cond.dim() == 1, "cond must be 1-D");
   const int n = (int)indptr.size(0) - 1;
   TORCH_CHECK(cond.size(0) == n);
   launch_k5(reinterpret_cast<const long long*>(indptr.data_ptr<int64_t>()),

@@ -411,3 +411,377 @@ def assert_colsum(tag, sums, F_after):
     err = np.abs(np.asarray(sums, dtype=np.float64) - ref)
     assert (err <= tol).all(), (
         f"{tag}: column sum off at {np.flatnonzero(err > tol)[:8].tolist()}")
+
+
+# ===========================================================================
+# K5 / K6 / K7 fixtures (docs/kernels.md, "K5 / K6 / K7 contract").  The
+# kernels that bracket the sweep produce integers, exact 0/1 values or one
+# IEEE division of exact integers, so everything built here is compared
+# with exact equality (tests/test_init_extract_oracle.py on the CPU,
+# tests/test_gpu_init_extract.py on the device).
+
+# ------------------------------------------------------------------ K7 rows
+K7_BLOCK = 256  # threads per row; each owns chunk = ceil(k_true/256) columns
+# membership_threshold(149, 1200) = 0.33944688306...: its fp32 rounding lies
+# BELOW it, so an entry equal to float32(delta) is a member under the fp32
+# rule and is not under an fp64 comparison.
+K7_DELTA = float(np.sqrt(-np.log1p(-2.0 * 1200 / (149 * 148))))
+assert float(np.float32(K7_DELTA)) < K7_DELTA
+# chunk: 1 (<= 256), 2 (257..512), 3 (513), 20 (5000, 5001), 98 (25000)
+K7_WIDTHS = (1, 2, 255, 256, 257, 511, 512, 513, 5000, 5001, 25000)
+K7_WIDE_LD = (257, 5000)  # also run with ldF = width + 24
+
+
+def k7_cases():
+    """(k_true, kp, dtype) of every K7 fixture.  The wide-ld cases add 24
+    to k_true (fp32; 281 is an odd row stride) or to the padded width
+    (bf16: a bf16 row stride must be even, K7 reads 32-bit words)."""
+    out = []
+    for dtype in ("fp32", "bf16"):
+        out += [(k, padded_k(k, dtype), dtype) for k in K7_WIDTHS]
+        out += [((k, k + 24, dtype) if dtype == "fp32"
+                 else (k, padded_k(k, dtype) + 24, dtype)) for k in K7_WIDE_LD]
+    return out
+
+
+def k7_id(t) -> str:
+    return f"k{t[0]}-ld{t[1]}-{t[2]}"
+
+
+def k7_chunk(k_true: int) -> int:
+    return -(-k_true // K7_BLOCK)
+
+
+def _f32_bits(x) -> int:
+    return int(np.array(x, dtype=np.float32).view(np.uint32))
+
+
+def _from_bits(b: int) -> float:
+    return float(np.array(b, dtype=np.uint32).view(np.float32))
+
+
+def bf16_ceil(x: float) -> float:
+    """Smallest bf16 value >= the positive fp32 value x."""
+    b = _f32_bits(x)
+    lo = b & 0xFFFF0000
+    return _from_bits(lo if lo == b else lo + 0x10000)
+
+
+def bf16_below(x: float) -> float:
+    """Largest bf16 value < the positive fp32 value x."""
+    b = _f32_bits(x)
+    lo = b & 0xFFFF0000
+    return _from_bits(lo - 0x10000 if lo == b else lo)
+
+
+def k7_values(dtype: str, delta: float = K7_DELTA) -> dict:
+    """The special values of the K7 rows, each representable in ``dtype``:
+    ``at`` the smallest value that is a member, ``below`` the largest that
+    is not, ``hi`` about 2t, ``lo`` > ``lo2`` well below t, ``tiny`` the
+    smallest positive normal."""
+    t = float(np.float32(delta))
+    if dtype == "bf16":
+        v = dict(at=bf16_ceil(t), below=bf16_below(t),
+                 hi=bf16_ceil(float(np.float32(2 * t))))
+    else:
+        v = dict(at=t, below=float(np.nextafter(np.float32(t), np.float32(0))),
+                 hi=float(np.float32(2 * t)))
+    v.update(t=t, lo=0.125, lo2=0.0625, tiny=2.0 ** -126)
+    assert v["tiny"] < v["lo2"] < v["lo"] < v["below"] < t <= v["at"] < v["hi"]
+    return v
+
+
+@functools.lru_cache(maxsize=None)
+def _k7_build(k_true: int, kp: int, dtype: str, delta: float):
+    v = k7_values(dtype, delta)
+    at, below, hi, lo, lo2 = v["at"], v["below"], v["hi"], v["lo"], v["lo2"]
+    chunk = k7_chunk(k_true)
+    last = k_true - 1
+    nthr = -(-k_true // chunk)  # threads that own at least one column
+    tm = (nthr - 1) // 2  # a mid-row thread with a right neighbour
+    m0 = tm * chunk  # first / last column of its chunk, and a middle one
+    m1 = min(m0 + chunk, k_true) - 1
+    mm = min(m0 + chunk // 2, last)
+    firsts = np.arange(0, k_true, chunk)
+    lasts = np.minimum(firsts + chunk, k_true) - 1
+    rows, names = [], []
+
+    def add(name, base, **cols):
+        r = np.full(k_true, base, dtype=np.float64)
+        for val, idx in cols.values():
+            r[idx] = val
+        rows.append(r)
+        names.append(name)
+
+    # plain membership
+    add("zero", 0.0)
+    add("member-col0", 0.0, a=(hi, 0))
+    add("member-last", 0.0, a=(hi, last))
+    add("member-chunk-first", 0.0, a=(hi, m0))
+    add("member-chunk-last", 0.0, a=(hi, m1))
+    # firsts sit exactly on the threshold, lasts well above it (chunk 1:
+    # first == last, so odd columns take the high value)
+    add("member-every-chunk-end", 0.0, a=(at, firsts),
+        b=(hi, lasts if chunk > 1 else np.arange(1, k_true, 2)))
+    add("member-all", at)
+    # threshold
+    add("exact-t", below, a=(at, mm))
+    add("just-below-t", lo, a=(below, mm))
+    # fallback: nothing reaches t
+    add("fallback-col0", lo2, a=(lo, 0))
+    add("fallback-last", lo2, a=(lo, last))
+    add("fallback-mid-chunk", lo2, a=(lo, mm))
+    add("fallback-tie-in-chunk", lo2, a=(lo, [m0, m1]))
+    add("fallback-tie-across-threads", lo2, a=(lo, [m1, min(m1 + 1, last)]))
+    e = mm & ~1
+    add("fallback-tie-bf16-word", lo2, a=(lo, [e, min(e + 1, last)]))
+    add("fallback-all-tied", lo)
+    add("fallback-min-normal", 0.0, a=(v["tiny"], mm))
+    if kp > k_true:
+        add("pads-only", 0.0)  # its only large values are the poisoned pads
+    exact_rows = len(rows)
+    rng = np.random.default_rng(7000 + k_true + (dtype == "bf16"))
+    for i in range(4):
+        r = rng.uniform(0.0, 2 * v["t"], size=k_true)
+        add(f"random-sparse-{i}", 0.0,
+            a=(r, slice(None)), b=(0.0, rng.random(k_true) < 0.9))
+    for i in range(4):
+        add(f"random-dense-{i}", 0.0,
+            a=(rng.uniform(0.0, 2 * v["t"], size=k_true), slice(None)))
+    # zero-count and full rows alternate: consecutive offsets repeat
+    for i in range(3):
+        add(f"tail-zero-{i}", 0.0)
+        add(f"tail-full-{i}", hi)
+    F = np.full((len(rows), kp), hi, dtype=np.float32)  # pads poisoned: 2t
+    F[:, :k_true] = np.stack(rows)
+    sd = torch.bfloat16 if dtype == "bf16" else torch.float32
+    Ft = torch.from_numpy(F).to(sd)
+    back = Ft.double().numpy()
+    assert (back[:exact_rows, :k_true] == np.stack(rows[:exact_rows])).all(), (
+        "a structured K7 value is not representable in " + dtype)
+    assert (back[:, k_true:] == hi).all() and len(rows) <= 64
+    return Ft, tuple(names)
+
+
+def k7_rows(k_true: int, kp: int, dtype: str, delta: float = K7_DELTA):
+    """[<= 64, kp] CPU tensor in the storage dtype (shared: do not modify).
+    Column positions follow chunk = ceil(k_true/256); pad columns
+    [k_true, kp) of every row hold 2t."""
+    return _k7_build(k_true, kp, dtype, float(delta))[0]
+
+
+def k7_row_names(k_true: int, kp: int, dtype: str, delta: float = K7_DELTA):
+    return _k7_build(k_true, kp, dtype, float(delta))[1]
+
+
+# ---------------------------------------------------------------- K5 graphs
+def _csr_graph(n: int, src, dst) -> Graph:
+    """Canonical CSR (sorted rows) from DIRECTED pairs holding both
+    directions of every edge.  Built directly, like ladder_graph, so
+    isolated ids survive."""
+    src = np.asarray(src, dtype=np.int64)
+    dst = np.asarray(dst, dtype=np.int64)
+    o = np.lexsort((dst, src))
+    src, dst = src[o], dst[o]
+    assert not ((src[1:] == src[:-1]) & (dst[1:] == dst[:-1])).any()
+    assert not (src == dst).any()
+    indptr = np.zeros(n + 1, dtype=np.int64)
+    np.add.at(indptr, src + 1, 1)
+    return Graph(indptr=np.cumsum(indptr), indices=dst.astype(np.int32),
+                 raw_ids=np.arange(n, dtype=np.int64))
+
+
+def _clique_pairs(nodes):
+    nodes = np.asarray(nodes, dtype=np.int64)
+    a, b = np.meshgrid(nodes, nodes, indexing="ij")
+    m = a != b
+    return a[m], b[m]
+
+
+def _hub_pool():
+    """The hub ladder's leaf pool in join order (centre d joins the first d
+    of it): the permutation ladder_graph drew."""
+    g, label = ladder_graph("hub")
+    n = g.num_nodes
+    perm = np.random.default_rng(1234 + len(HUB_DEGREES)).permutation(n)
+    pool = perm[: max(HUB_DEGREES)]
+    c65 = int(np.flatnonzero(label == 65)[0])
+    assert set(g.neighbors(c65).tolist()) == set(pool[:65].tolist())
+    return pool
+
+
+@functools.lru_cache(maxsize=None)
+def k5_graphs() -> dict:
+    """name -> Graph, all canonical with sorted rows."""
+    from bigclam.io import rmat_graph
+
+    out = {"ladder-small": ladder_graph("small")[0],
+           "ladder-hub": ladder_graph("hub")[0]}
+    # complete graphs: every search hits, vol_T == 0, neighbour rows of
+    # length 64 (K65) and 65 (K66)
+    for m in (2, 3, 65, 66):
+        out[f"K{m}"] = _csr_graph(m, *_clique_pairs(np.arange(m)))
+    # star: the centre's row is 257 long (5 lane rounds), centre id inside
+    # the id range so leaves miss on both sides
+    centre = 100
+    leaves = np.setdiff1d(np.arange(258), [centre])
+    out["star257"] = _csr_graph(
+        258, np.concatenate([np.full(257, centre), leaves]),
+        np.concatenate([leaves, np.full(257, centre)]))
+    # two K20 joined by one bridge: 0 < cond < 1
+    s0, d0 = _clique_pairs(np.arange(20))
+    s1, d1 = _clique_pairs(np.arange(20, 40))
+    out["two-K20"] = _csr_graph(
+        40, np.concatenate([s0, s1, [5, 30]]),
+        np.concatenate([d0, d1, [30, 5]]))
+    # hub ladder + a clique over the first 70 pool leaves: triangles on the
+    # centres, so searches hit at both ends of long rows
+    hub = out["ladder-hub"]
+    hs = np.repeat(np.arange(hub.num_nodes), np.diff(hub.indptr))
+    cs, cd = _clique_pairs(_hub_pool()[:70])
+    out["clique-ladder"] = _csr_graph(
+        hub.num_nodes, np.concatenate([hs, cs]),
+        np.concatenate([hub.indices.astype(np.int64), cd]))
+    out["rmat9"] = rmat_graph(9, 6.0, seed=31)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def k5_oracle(name: str) -> dict:
+    """The integer oracle on one K5 graph: deg, z, cut int64 [N] and cond
+    float64 [N] (computed once per process)."""
+    import oracle
+
+    g = k5_graphs()[name]
+    rows = [oracle.conductance_int(g.indptr, g.indices, u)
+            for u in range(g.num_nodes)]
+    deg, z, cut, cond = (np.array(c) for c in zip(*rows))
+    return dict(deg=deg.astype(np.int64), z=z.astype(np.int64),
+                cut=cut.astype(np.int64), cond=cond.astype(np.float64))
+
+
+@functools.lru_cache(maxsize=None)
+def k5_fixture_conditions() -> dict:
+    """Which kernel edges the K5 graph set reaches (condition -> the first
+    graph that shows it, or None).  A search is the lookup of a 2-hop
+    endpoint w != u in u's sorted row."""
+    found = {}
+
+    def mark(cond, name):
+        found.setdefault(cond, name)
+
+    for name, g in k5_graphs().items():
+        o = k5_oracle(name)
+        vol_s = o["z"] - o["cut"]
+        vol_t = len(g.indices) - vol_s - 2 * o["cut"]
+        assert (vol_t >= 0).all()  # the max(.., 1) guard cannot fire
+        assert ((vol_s == 0) == (o["deg"] == 0)).all()
+        if (o["deg"] == 0).any():
+            mark("deg==0", name)
+        if ((vol_t == 0) & (o["deg"] > 0)).any():
+            mark("vol_T==0", name)
+        if ((o["cond"] > 0) & (o["cond"] < 1)).any():
+            mark("0<cond<1", name)
+        if (o["cond"] > 1).any():
+            mark("cond>1", name)
+        for d in (1, 2, 3, 4, 5):
+            if (o["deg"] == d).any():
+                mark(f"deg(u)=={d}", name)
+        deg = np.diff(g.indptr)
+        for u in range(g.num_nodes):
+            nu = g.neighbors(u)
+            if not len(nu):
+                continue
+            for ln in (63, 64, 65):
+                if (deg[nu] == ln).any():
+                    mark(f"neighbour row of {ln}", name)
+            w = np.concatenate([g.neighbors(int(v)) for v in nu])
+            w = w[w != u]
+            if (w == nu[0]).any():
+                mark("hit on first", name)
+            if (w == nu[-1]).any():
+                mark("hit on last", name)
+            if (w < nu[0]).any():
+                mark("miss below", name)
+            if (w > nu[-1]).any():
+                mark("miss above", name)
+    return found
+
+
+K5_CONDITIONS = (
+    "deg==0", "vol_T==0", "0<cond<1", "cond>1", "hit on first",
+    "hit on last", "miss below", "miss above", "neighbour row of 63",
+    "neighbour row of 64", "neighbour row of 65", "deg(u)==1", "deg(u)==2",
+    "deg(u)==3", "deg(u)==4", "deg(u)==5")
+
+
+def assert_k5_fixture_conditions():
+    found = k5_fixture_conditions()
+    missing = [c for c in K5_CONDITIONS if c not in found]
+    assert not missing, f"K5 graphs never reach: {missing}"
+
+
+# ----------------------------------------------------------------- K6 cases
+K6_KP = {8: 8, 37: 40, 600: 608}  # number of seeds -> padded width
+
+
+@functools.lru_cache(maxsize=None)
+def k6_seed_lists() -> dict:
+    """number of seeds -> int64 seed list on the hub ladder.  Every list
+    starts with the centres of degree 1, 255, 256, 257, 513 and 600, one
+    leaf and one isolated node; the 600-seed list (more than one 256-column
+    round, longer than a block) repeats nodes, which is fine: columns
+    differ."""
+    g, label = ladder_graph("hub")
+    base = [int(np.flatnonzero(label == d)[0])
+            for d in (1, 255, 256, 257, 513, 600)]
+    base += [int(np.flatnonzero(label == -1)[0]),
+             int(np.flatnonzero(label == -2)[0])]
+    rest = [int(u) for u in np.flatnonzero(label >= 0) if int(u) not in base]
+    rest += [int(u) for u in np.flatnonzero(label == -1)[1:11]]
+    rng = np.random.default_rng(600)
+    many = base + rng.integers(0, g.num_nodes, size=592).tolist()
+    out = {8: base, 37: base + rest[:29], 600: many}
+    assert all(len(v) == k for k, v in out.items())
+    return {k: np.asarray(v, dtype=np.int64) for k, v in out.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def k6_shards() -> dict:
+    """Row ranges on the hub ladder: the whole graph, a 3-way split whose
+    middle shard [a, b) has seed neighbours exactly on a (start), b - 1
+    (stop - 1) and b (stop), and the empty shard (a, a)."""
+    g, label = ladder_graph("hub")
+    n = g.num_nodes
+    nb = set(g.neighbors(int(np.flatnonzero(label == 600)[0])).tolist())
+    a = next(x for x in range(n // 3, n) if x in nb)
+    b = next(x for x in range(2 * n // 3, n - 1) if x in nb and x - 1 in nb)
+    assert 0 < a < b - 1 < b < n
+    return {"full": (0, n), "split": ((0, a), (a, b), (b, n)),
+            "empty": (a, a)}
+
+
+@functools.lru_cache(maxsize=None)
+def k7_oracle(k_true: int, kp: int, dtype: str):
+    """oracle.memberships on one K7 fixture (computed once per process)."""
+    import oracle
+
+    F = k7_rows(k_true, kp, dtype)
+    return oracle.memberships(F.double().numpy(), k_true, K7_DELTA)
+
+
+@functools.lru_cache(maxsize=None)
+def k6_oracle(n_seeds: int, shard: tuple, include_seed: bool, fill: float):
+    """oracle.seed_scatter on the hub ladder at the padded width of the
+    seed list (computed once per process)."""
+    import oracle
+
+    g, _ = ladder_graph("hub")
+    return oracle.seed_scatter(g.indptr, g.indices, k6_seed_lists()[n_seeds],
+                               shard[0], shard[1], K6_KP[n_seeds],
+                               include_seed, fill)
+
+
+def k6_all_shards():
+    s = k6_shards()
+    return (s["full"],) + s["split"] + (s["empty"],)

@@ -413,3 +413,81 @@ def pick_cap_ok(n_differ, n_nodes, dtype):
     if n_nodes < 100:
         return n_differ <= 2
     return n_differ <= PICK_CAP[dtype] * n_nodes
+
+
+# ---------------------------------------------------------------------------
+# Exact oracles of the kernels that bracket the sweep (docs/kernels.md,
+# "K5 / K6 / K7 contract").  K5 produces one IEEE division of exact
+# integers, K6 exact 0/1 values, K7 integers: every comparison against
+# these is exact equality, no tolerance anywhere.  Plain loops, slow on
+# purpose.
+def memberships(F64, k_true, delta):
+    """K7 oracle.  ``F64``: the STORED values upcast exactly, [n, >=k_true].
+    The threshold is ``delta`` rounded to fp32 — what the kernel compares
+    against (``(float)delta``) and what a torch fp32 comparison with a
+    Python float does.  Row rule: members are the columns < k_true with
+    f >= t; if there are none and the row max over [:k_true] is > 0,
+    members are the columns equal to that max; otherwise none.
+    Returns (counts int64 [n], comms int32 [total]), row-major ascending."""
+    F64 = np.asarray(F64, dtype=np.float64)
+    t = float(np.float32(delta))
+    counts = np.zeros(F64.shape[0], dtype=np.int64)
+    comms = []
+    for u in range(F64.shape[0]):
+        row = F64[u, :k_true].tolist()
+        mem =[c for c in range(k_true) if row[c] >= t]
+        if not mem:
+            fmax = max(row) if k_true else 0.0
+            if fmax > 0:
+                mem = [c for c in range(k_true) if row[c] == fmax]
+        counts[u] = len(mem)
+        comms += mem
+    return counts, np.asarray(comms, dtype=np.int32)
+
+
+def conductance_int(indptr, indices, u):
+    """K5 oracle: ``(deg, z_size, cut, cond)`` of node u from the
+    brute-force 2-hop walk over the closed ego-net y = {u} ∪ N(u); the
+    three counts are Python ints, cond follows from them by the documented
+    guards (vol_S == 0 -> 0, vol_T == 0 -> 1).  All integers are far below
+    2^53 and the kernel performs one double division of the same integers,
+    so a device cond must be BITWISE equal.  No max(.., 1) guard: vol_T =
+    sum of outside degrees - cut >= 0, and two non-zero volumes are >= 1,
+    so it cannot fire."""
+    total_degree = int(len(indices))
+    nbrs = indices[indptr[u] : indptr[u + 1]]
+    deg = int(len(nbrs))
+    inside = np.zeros(len(indptr) - 1, dtype=bool)
+    inside[u] = True
+    inside[nbrs] = True
+    z_size = 0
+    cut = 0
+    for m in np.flatnonzero(inside):
+        row = indices[indptr[m] : indptr[m + 1]]
+        z_size += int(len(row))
+        cut += int(np.count_nonzero(~inside[row]))
+    vol_s = z_size - cut
+    vol_t = total_degree - vol_s - 2 * cut
+    if vol_s == 0:
+        cond = 0.0
+    elif vol_t == 0:
+        cond = 1.0
+    else:
+        cond = float(np.float64(cut) / np.float64(min(vol_s, vol_t)))
+    return deg, z_size, cut, cond
+
+
+def seed_scatter(indptr, indices, seeds, start, stop, kp, include_seed, fill):
+    """K6 oracle: an [stop-start, kp] fp64 array pre-filled with ``fill``;
+    column c gets 1.0 in the rows of N(seeds[c]) (and of seeds[c] itself
+    with ``include_seed``) that lie in [start, stop)."""
+    out = np.full((stop - start, kp), float(fill), dtype=np.float64)
+    for c, s in enumerate(seeds):
+        s = int(s)
+        for v in indices[indptr[s] : indptr[s + 1]]:
+            v = int(v)
+            if start <= v < stop:
+                out[v - start, c] = 1.0
+        if include_seed and start <= s < stop:
+            out[s - start, c] = 1.0
+    return out
