@@ -413,6 +413,88 @@ def assert_colsum(tag, sums, F_after):
         f"{tag}: column sum off at {np.flatnonzero(err > tol)[:8].tolist()}")
 
 
+class Judge:
+    """Oracle of one (F, sumF, CSR) with margins cached per distinct
+    (grad, llh) — paths sharing phase A bitwise share one margin pass."""
+
+    def __init__(self, F, sumF, indptr, indices, cfg, label, k, dtype,
+                 n_local=None):
+        import oracle
+
+        self.F64 = F.double().cpu().numpy()
+        self.s64 = sumF.double().cpu().numpy()
+        self.indptr, self.indices = np.asarray(indptr), np.asarray(indices)
+        self.cfg, self.label, self.k, self.dtype = cfg, label, k, dtype
+        self.n_local = n_local
+        self.o = oracle.vec_grad_llh(self.F64, self.s64, self.indptr,
+                                     self.indices, cfg, n_local=n_local)
+        self._mo = {}
+
+    def margins(self, grad, llh):
+        import oracle
+
+        key = (hash(grad.tobytes()), hash(llh.tobytes()))
+        if key not in self._mo:
+            self._mo[key] = oracle.vec_margins(
+                self.F64, self.s64, self.indptr, self.indices, self.cfg,
+                grad, llh, n_local=self.n_local)
+        return self._mo[key]
+
+    def check(self, tag, grad, llh, best=None, bf16_candidates=False,
+              rows=None, check_grad=True):
+        """Returns the figures it printed: (largest normalised grad error,
+        largest normalised llh error, picks differing from the exact pick
+        or None)."""
+        import oracle
+
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        g = grad.cpu().numpy()
+        l = llh.cpu().numpy()
+        # the figures first (pytest -s shows them), then the assertions
+        o = self.o
+        sel = slice(None) if rows is None else rows
+        with np.errstate(invalid="ignore", divide="ignore"):
+            eg = np.nanmax((np.abs(g - o["grad"]) / (oracle.EPS32 * o["A"]))[sel]
+                           ) if check_grad else float("nan")
+            el = np.nanmax((np.abs(l - o["llh"]) / (oracle.EPS32 * o["L"]))[sel])
+        msg = f"{tag}: grad {eg:.1f}/{oracle.C_GRAD:g} llh {el:.1f}/{oracle.C_LLH:g}"
+        nd = None
+        if best is not None:
+            mo = self.margins(g, l)
+            rung = oracle.steps_to_rungs(best.cpu().numpy(), self.cfg)
+            nd = int((rung != mo['pick'])[sel].sum())
+            msg += f" picks differing {nd}"
+        print(msg)
+        assert_grad_llh(tag, self.o, self.indptr, self.label, self.k,
+                        g if check_grad else None, l, rows=rows)
+        if best is not None:
+            assert_picks(tag, self.margins(g, l), self.indptr, self.label,
+                         self.cfg, self.dtype, best.cpu().numpy(),
+                         bf16_candidates=bf16_candidates, rows=rows)
+        return float(eg), float(el), nd
+
+
+def rescan(Fh, r):
+    """(columns, values) of row r's non-zeros, ascending — what KAF emits."""
+    ks = np.flatnonzero(Fh[r])
+    return ks, Fh[r, ks]
+
+
+def assert_lists(tag, Fh, rows, scount, sidx, sval, cap):
+    """Counts and lists of ``rows`` equal a numpy rescan of F (ascending
+    columns); an over-cap row has its count only.  ``rows`` index the
+    buffer the pools belong to: owned rows and, past n_local, halo rows."""
+    for r in rows:
+        ks, vs = rescan(Fh, r)
+        assert scount[r] == len(ks), f"{tag}: row {r} count"
+        if len(ks) > cap:
+            continue
+        sl = slice(r * cap, r * cap + len(ks))
+        np.testing.assert_array_equal(sidx[sl], ks, err_msg=f"{tag}: row {r}")
+        np.testing.assert_array_equal(sval[sl], vs, err_msg=f"{tag}: row {r}")
+
+
 # ===========================================================================
 # K5 / K6 / K7 fixtures (docs/kernels.md, "K5 / K6 / K7 contract").  The
 # kernels that bracket the sweep produce integers, exact 0/1 values or one

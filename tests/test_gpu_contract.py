@@ -47,53 +47,7 @@ def _state(case):
     return cfg, st
 
 
-class _Judge:
-    """Oracle of one (F, sumF, CSR) with margins cached per distinct
-    (grad, llh) — paths sharing phase A bitwise share one margin pass."""
-
-    def __init__(self, F, sumF, indptr, indices, cfg, label, k, dtype,
-                 n_local=None):
-        self.F64 = F.double().cpu().numpy()
-        self.s64 = sumF.double().cpu().numpy()
-        self.indptr, self.indices = np.asarray(indptr), np.asarray(indices)
-        self.cfg, self.label, self.k, self.dtype = cfg, label, k, dtype
-        self.n_local = n_local
-        self.o = oracle.vec_grad_llh(self.F64, self.s64, self.indptr,
-                                     self.indices, cfg, n_local=n_local)
-        self._mo = {}
-
-    def margins(self, grad, llh):
-        key = (hash(grad.tobytes()), hash(llh.tobytes()))
-        if key not in self._mo:
-            self._mo[key] = oracle.vec_margins(
-                self.F64, self.s64, self.indptr, self.indices, self.cfg,
-                grad, llh, n_local=self.n_local)
-        return self._mo[key]
-
-    def check(self, tag, grad, llh, best=None, bf16_candidates=False,
-              rows=None, check_grad=True):
-        torch.cuda.synchronize()
-        g = grad.cpu().numpy()
-        l = llh.cpu().numpy()
-        # the figures first (pytest -s shows them), then the assertions
-        o = self.o
-        sel = slice(None) if rows is None else rows
-        with np.errstate(invalid="ignore", divide="ignore"):
-            eg = np.nanmax((np.abs(g - o["grad"]) / (oracle.EPS32 * o["A"]))[sel]
-                           ) if check_grad else float("nan")
-            el = np.nanmax((np.abs(l - o["llh"]) / (oracle.EPS32 * o["L"]))[sel])
-        msg = f"{tag}: grad {eg:.1f}/{oracle.C_GRAD:g} llh {el:.1f}/{oracle.C_LLH:g}"
-        if best is not None:
-            mo = self.margins(g, l)
-            rung = oracle.steps_to_rungs(best.cpu().numpy(), self.cfg)
-            msg += f" picks differing {(rung != mo['pick'])[sel].sum()}"
-        print(msg)
-        cf.assert_grad_llh(tag, self.o, self.indptr, self.label, self.k,
-                           g if check_grad else None, l, rows=rows)
-        if best is not None:
-            cf.assert_picks(tag, self.margins(g, l), self.indptr, self.label,
-                            self.cfg, self.dtype, best.cpu().numpy(),
-                            bf16_candidates=bf16_candidates, rows=rows)
+_Judge = cf.Judge  # moved to the shared fixtures: the CPU lockstep tests use it too
 
 
 def _run_paths(case, monkeypatch, extras):

@@ -34,23 +34,8 @@ def _bits(F):
     return F.view(torch.int16 if F.dtype == torch.bfloat16 else torch.int32)
 
 
-def _rescan(Fh, r):
-    """(columns, values) of row r's non-zeros, ascending — what KAF emits."""
-    ks = np.flatnonzero(Fh[r])
-    return ks, Fh[r, ks]
-
-
-def _assert_lists(tag, Fh, rows, scount, sidx, sval, cap):
-    """Counts and lists of ``rows`` equal a numpy rescan of F (ascending
-    columns); an over-cap row has its count only."""
-    for r in rows:
-        ks, vs = _rescan(Fh, r)
-        assert scount[r] == len(ks), f"{tag}: row {r} count"
-        if len(ks) > cap:
-            continue
-        sl = slice(r * cap, r * cap + len(ks))
-        np.testing.assert_array_equal(sidx[sl], ks, err_msg=f"{tag}: row {r}")
-        np.testing.assert_array_equal(sval[sl], vs, err_msg=f"{tag}: row {r}")
+_rescan = cf.rescan  # moved to the shared fixtures (sharded tests)
+_assert_lists = cf.assert_lists
 
 
 # ------------------------------------------- 1. wave commit == block commit
