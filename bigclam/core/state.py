@@ -134,6 +134,7 @@ class ShardState:
         # native routing buffers (allocated once, by the first routed
         # sweep) and the two alternating by-class order buffers' index
         self._rt: Optional[dict] = None
+        self._wave_split = None
         self._rt_flip = 0
         self._sumF_buf: Optional[torch.Tensor] = None  # stage-2 target
         self._sp_scount: Optional[torch.Tensor] = None
@@ -421,11 +422,14 @@ class ShardState:
         + stable sort), the A/B switch and the tests' reference."""
         return os.environ.get("BIGCLAM_NATIVE_ROUTE", "1") != "0"
 
-    def _route_native(self, scount, cap, wcap):
+    def _route_native(self, scount, cap, wcap, qcap=0):
         """One routing pass on the device: returns (epre, bound32,
         by_class, GG, n_block, n_s).  by_class alternates between two
         buffers so a carried pack's ``order``/``order_d`` stay valid
-        until that pack is committed and read."""
+        until that pack is committed and read.  With ``qcap > 0`` the
+        same pass splits the wave class for the packed kernel and leaves
+        ``(wsplit, n_pack)`` in ``self._wave_split`` (read by this sweep's
+        fused launch only, so one buffer serves)."""
         ext = _hip_ops().ensure_loaded()
         rt = self._rt
         if rt is None:
@@ -442,14 +446,18 @@ class ShardState:
                 "totals": torch.empty(3, **i32),
                 "GG": torch.empty(1, device=dev, dtype=torch.float32),
                 "by_class": [torch.empty(n, **i32) for _ in range(2)],
+                "wsplit": torch.empty(n, **i32),
+                "pscr": torch.empty(4 * (nt3 // 3) + 1, **i32),
             }
         self._rt_flip ^= 1
         by_class = rt["by_class"][self._rt_flip]
-        n_blk, n_wave, _ = ext.sparse_route(
+        split = (qcap, rt["wsplit"], rt["pscr"]) if qcap > 0 else ()
+        n_blk, n_wave, _, *n_pack = ext.sparse_route(
             self.indptr, self.indices, scount, self.order, self.sumF,
             cap, wcap, rt["epre"], rt["bound"], rt["cls"], rt["tcount"],
-            rt["tbase"], rt["totals"], rt["GG"], by_class,
+            rt["tbase"], rt["totals"], rt["GG"], by_class, *split,
         )  # <- the one host sync
+        self._wave_split = (rt["wsplit"], n_pack[0]) if n_pack else None
         return rt["epre"], rt["bound"], by_class, rt["GG"], n_blk, \
             n_blk + n_wave
 
@@ -527,6 +535,37 @@ class ShardState:
         fixed = lds(bf, self.kp, 0)
         per = lds(bf, self.kp, 1) - fixed
         return max(0, min(w, self.sparse_cap, (65536 - fixed) // per))
+
+    # bitmap words above which the packed kernel stays off by default (its
+    # bitmap passes run on 16 lanes per node instead of 64).  Measured at
+    # K=25000 it wins with qcap=64 forced; the default has not been run
+    # through the large-K tests there yet (profiles/r08_kfp_pack.md)
+    _QCAP_MAX_NW = 256
+
+    @property
+    def sparse_qcap(self) -> int:
+        """Slot cap of the packed wave kernel (KFP, four nodes per wave):
+        wave-class nodes with bound <= qcap and degree <= 16 run there,
+        the rest of the wave class on KFW.  0 disables KFP.
+        BIGCLAM_SPARSE_QCAP overrides the default; the value is clamped to
+        ``sparse_wcap`` and to what fits a 64 KB workgroup by the
+        launcher's own size formula.  Off with BIGCLAM_NATIVE_ROUTE=0:
+        the torch routing is the A/B reference and has no split."""
+        if not self.use_hip or not self.native_route:
+            return 0
+        env = os.environ.get("BIGCLAM_SPARSE_QCAP")
+        if env is not None:
+            q = int(env)
+        else:
+            q = 64 if (self.kp + 31) // 32 <= self._QCAP_MAX_NW else 0
+        if q <= 0:
+            return 0
+        lds = _hip_ops().ensure_loaded().sparse_pack_lds_bytes
+        bf = self.storage_dtype == torch.bfloat16
+        fixed = lds(bf, self.kp, 0)
+        per4 = lds(bf, self.kp, 4) - fixed  # the formula steps by 4 slots
+        fit = (65536 - fixed) // per4 * 4 if fixed < 65536 else 0
+        return max(0, min(q, self.sparse_wcap, fit))
 
     @property
     def sparse_allowed(self) -> bool:
@@ -710,8 +749,17 @@ class ShardState:
         # order out as [block | wave | dense]; the class sizes are the
         # sweep's one routing host sync.
         wcap = self.sparse_wcap
-        route = self._route_native if self.native_route else self._route_torch
-        epre, bound32, by_class, GG, n_blk, n_s = route(scount, cap, wcap)
+        qcap = self.sparse_qcap
+        self._wave_split = None
+        if self.native_route:
+            epre, bound32, by_class, GG, n_blk, n_s = self._route_native(
+                scount, cap, wcap, qcap
+            )
+        else:
+            epre, bound32, by_class, GG, n_blk, n_s = self._route_torch(
+                scount, cap, wcap
+            )
+        wsplit, n_pack = self._wave_split or (None, 0)
         order_s = by_class[:n_s]
         # engage only when a real fraction of nodes routes: at low K /
         # moderate density the bound exceeds cap for most nodes and the
@@ -765,9 +813,12 @@ class ShardState:
             self.n_local * cap, cap, llh, best, self.cfg,
             state_pools=(self._sp_gidx, self._sp_gval),
             n_block=n_blk, wcap=wcap, GG=GG,
+            qcap=qcap if wsplit is not None else 0, wsplit=wsplit,
+            n_pack=n_pack,
         )
         pack["n_block"] = n_blk  # order[:n_block] block class, rest wave
         pack["wcap"] = wcap
+        pack["n_pack"] = n_pack  # wave-class nodes run four per wave
         if n_d:
             torch.cuda.current_stream(dev).wait_stream(self._side_stream)
         pack["best"] = best

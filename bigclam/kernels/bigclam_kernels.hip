@@ -2567,6 +2567,7 @@ __global__ void __launch_bounds__(BLOCK) kaf_support_t(
 #define RT_GRP 16      // lanes per node in the bounds walk
 #define RT_HUB 512     // degree above which the whole block walks the node
 #define RT_SCAN 1024   // threads of the single scan block
+#define KFP_DEG 16     // most edges of a node on the packed wave path (KFP)
 
 __device__ __forceinline__ int sat_add(int a, int b, int sat) {
   return min(a + b, sat);
@@ -2581,7 +2582,7 @@ __global__ void __launch_bounds__(BLOCK) kr_bounds(
     const int* __restrict__ scount, const int* __restrict__ order,
     int n_local, int cap, int wcap, int* __restrict__ epre,
     int* __restrict__ bound, unsigned char* __restrict__ cls,
-    int* __restrict__ tcount) {
+    int* __restrict__ tcount, int qcap, int* __restrict__ pscr) {
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   const int wid = tid >> 6;
@@ -2593,7 +2594,9 @@ __global__ void __launch_bounds__(BLOCK) kr_bounds(
   __shared__ int s_hub[RT_TILE];
   __shared__ int s_nhub;
   __shared__ int s_scan[NWAVE];
+  __shared__ unsigned char s_el[RT_TILE];  // packable (KFP) wave-class node
   if (tid == 0) s_nhub = 0;
+  if (tid < RT_TILE) s_el[tid] = 0;
   __syncthreads();
   constexpr int NGRP = BLOCK / RT_GRP;
   for (int r = 0; r < RT_TILE / NGRP; ++r) {
@@ -2625,7 +2628,10 @@ __global__ void __launch_bounds__(BLOCK) kr_bounds(
     if (gl == 0) {
       const int b = sat_add(min(scount[u], sat), carry, sat);
       bound[u] = b;
-      s_cls[q] = (unsigned char)route_class(b, cap, wcap);
+      const int c = route_class(b, cap, wcap);
+      s_cls[q] = (unsigned char)c;
+      s_el[q] = (unsigned char)(c == 1 && qcap > 0 && b <= qcap &&
+                                deg <= KFP_DEG);  // qcap 0: nothing packs
     }
   }
   __syncthreads();
@@ -2688,6 +2694,14 @@ __global__ void __launch_bounds__(BLOCK) kr_bounds(
     if (lane < 3)
       tcount[blockIdx.x * 3 + lane] =
           __popcll(lane == 0 ? m0 : (lane == 1 ? m1 : m2));
+    if (pscr) {  // the packed / single split of the wave class
+      const unsigned long long me = __ballot(p < n_local && s_el[lane]);
+      if (lane == 0) {
+        pscr[blockIdx.x * 3] = __popcll(me);
+        pscr[blockIdx.x * 3 + 1] = (int)(unsigned)(me & 0xffffffffull);
+        pscr[blockIdx.x * 3 + 2] = (int)(unsigned)(me >> 32);
+      }
+    }
   }
 }
 
@@ -2695,23 +2709,30 @@ __global__ void __launch_bounds__(BLOCK) kr_bounds(
 __global__ void __launch_bounds__(RT_SCAN) kr_scan(
     const int* __restrict__ tcount, int n_tiles, int* __restrict__ tbase,
     int* __restrict__ totals, const float* __restrict__ sumF, int K,
-    float* __restrict__ GG) {
+    float* __restrict__ GG, const int* __restrict__ pcnt,
+    int* __restrict__ pbase) {
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   const int wid = tid >> 6;
   constexpr int NW = RT_SCAN / WAVE;
   __shared__ int s_w[NW][3];
   __shared__ float s_g[NW];
+  __shared__ int s_p[NW];
   const int chunk = (n_tiles + RT_SCAN - 1) / RT_SCAN;
   const int t0 = min(tid * chunk, n_tiles);
   const int t1 = min(t0 + chunk, n_tiles);
   int c[3] = {0, 0, 0};
+  // packable counts ride along in the same loops (pcnt: 3 ints per tile =
+  // count, ballot lo, ballot hi; pbase: a base per tile, then the total)
+  int cp = 0;
   for (int t = t0; t < t1; ++t) {
     c[0] += tcount[t * 3];
     c[1] += tcount[t * 3 + 1];
     c[2] += tcount[t * 3 + 2];
+    if (pcnt) cp += pcnt[t * 3];
   }
   int incl[3] = {c[0], c[1], c[2]};
+  int inclp = cp;
 #pragma unroll
   for (int off = 1; off < WAVE; off <<= 1) {
 #pragma unroll
@@ -2719,6 +2740,8 @@ __global__ void __launch_bounds__(RT_SCAN) kr_scan(
       const int v = __shfl_up(incl[j], off, WAVE);
       if (lane >= off) incl[j] += v;
     }
+    const int vp = __shfl_up(inclp, off, WAVE);
+    if (lane >= off) inclp += vp;
   }
   // GG in a fixed order: strided per-thread sums, xor tree, waves in order
   float g = 0.f;
@@ -2730,6 +2753,7 @@ __global__ void __launch_bounds__(RT_SCAN) kr_scan(
     s_w[wid][1] = incl[1];
     s_w[wid][2] = incl[2];
     s_g[wid] = g;
+    s_p[wid] = inclp;
   }
   __syncthreads();
   int run[3];
@@ -2739,13 +2763,20 @@ __global__ void __launch_bounds__(RT_SCAN) kr_scan(
     for (int wv = 0; wv < wid; ++wv) b += s_w[wv][j];
     run[j] = b + incl[j] - c[j];
   }
+  int runp = inclp - cp;
+  for (int wv = 0; wv < wid; ++wv) runp += s_p[wv];
   for (int t = t0; t < t1; ++t) {
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       tbase[t * 3 + j] = run[j];
       run[j] += tcount[t * 3 + j];
     }
+    if (pcnt) {
+      pbase[t] = runp;
+      runp += pcnt[t * 3];
+    }
   }
+  if (pcnt && tid == RT_SCAN - 1) pbase[n_tiles] = runp;
   if (tid == 0) {
     float gs = 0.f;
     int tot[3] = {0, 0, 0};
@@ -2766,7 +2797,9 @@ __global__ void __launch_bounds__(RT_SCAN) kr_scan(
 __global__ void __launch_bounds__(BLOCK) kr_place(
     const int* __restrict__ order, const unsigned char* __restrict__ cls,
     const int* __restrict__ tbase, const int* __restrict__ totals,
-    int n_local, int n_tiles, int* __restrict__ by_class) {
+    int n_local, int n_tiles, int* __restrict__ by_class,
+    const int* __restrict__ pcnt, const int* __restrict__ pbase,
+    int* __restrict__ wsplit) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int tile = blockIdx.x * NWAVE + (threadIdx.x >> 6);
   if (tile >= n_tiles) return;  // wave-uniform
@@ -2781,6 +2814,18 @@ __global__ void __launch_bounds__(BLOCK) kr_place(
     const int cbase =
         (c >= 1 ? totals[0] : 0) + (c == 2 ? totals[1] : 0);
     by_class[cbase + tbase[tile * 3 + c] + rank] = order[p];
+    if (wsplit && c == 1) {
+      // stable two-way partition of the wave class: packable nodes'
+      // pack positions first, the others after, both in launch order
+      const int wrank = tbase[tile * 3 + 1] + rank;
+      const unsigned long long em =
+          ((unsigned long long)(unsigned)pcnt[tile * 3 + 2] << 32) |
+          (unsigned long long)(unsigned)pcnt[tile * 3 + 1];
+      const int eb = pbase[tile] + __popcll(em & ((1ull << lane) - 1ull));
+      const int slot =
+          ((em >> lane) & 1ull) ? eb : pbase[n_tiles] + (wrank - eb);
+      wsplit[slot] = totals[0] + wrank;
+    }
   }
 }
 
@@ -3123,7 +3168,7 @@ template <bool BF16>
 __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
     int K, const long long* __restrict__ indptr,
     const int* __restrict__ indices, const float* __restrict__ sumF,
-    const int* __restrict__ order, int blk0,
+    const int* __restrict__ order, int blk0, const int* __restrict__ pos,
     const long long* __restrict__ soffset, const int* __restrict__ sidx,
     const float* __restrict__ sval, const int* __restrict__ scount,
     const int* __restrict__ epre, const int* __restrict__ bound,
@@ -3133,7 +3178,8 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
     const float* __restrict__ GGp, const float* __restrict__ ladder,
     float* __restrict__ best, int n_ladder, int wcap, float alpha,
     float min_p, float max_p, float min_f, float max_f) {
-  const int b = blk0 + (int)blockIdx.x;  // position in the routed order
+  // position in the routed order: consecutive from blk0, or listed in pos
+  const int b = pos ? pos[blk0 + (int)blockIdx.x] : blk0 + (int)blockIdx.x;
   const int u = order[b];
   const long long e0 = indptr[u];
   const int deg = (int)(indptr[u + 1] - e0);
@@ -3366,6 +3412,328 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
   const unsigned long long bal = __ballot(ok) & 0xffffull;
   const float spick = __shfl(sj, bal ? __ffsll(bal) - 1 : 0, WAVE);
   if (lane == 0) best[u] = bal ? spick : 0.f;
+}
+
+// KFP: the KFW computation with FOUR nodes per wave, 16 lanes per node,
+// for the wave-class nodes that routing flags as packable (bound <= qcap
+// and degree <= KFP_DEG).  KFW's per-node instruction stream (prologue,
+// bitmap passes, scans, reductions, the Armijo tail) runs once per wave
+// whatever the node holds; here it runs once per four nodes.  Lanes
+// 16g..16g+15 belong to node g = pos[4*blockIdx.x + g]; a tail quad's dead
+// groups run masked (degree, support and staged total 0, no global
+// writes).  Loops that hold a cross-lane step run to the quad's largest
+// degree; a group past its own degree sees empty edges.
+//
+// Every output is BITWISE what KFW writes for the same node:
+//   * staging, bitmap, sorted compact set, rank by popcount: integers;
+//   * per-edge dot: 16-lane stride + xor 8/4/2/1, as in KFW; lane e of the
+//     group then holds x_e, so exp / 1/(1-p) / log1pf run once,
+//     lane-parallel over the (<= 16) edges;
+//   * scatter: edge by edge in CSR order, plain LDS read-add-write;
+//   * phase-3 sums: KFW's lane l takes i = l (mod 64) and folds by xor
+//     32, 16, 8..1; lane gl here keeps c0..c3 for i = gl + 16q (mod 64)
+//     and forms (c0 + c2) + (c1 + c3), then xor 8..1;
+//   * edge llh: KFW's four group leaders sum edges e = q (mod 4) in
+//     doubles and fold (A0 + A2) + (A1 + A3); lane q < 4 here sums
+//     l_q, l_q+4, l_q+8, l_q+12 in that order and folds the same way;
+//   * trials: KFW's lane (slot q, candidate j) sums edges e = q (mod 4)
+//     and node terms i = q (mod 4), folded by xor 16 then 32 =
+//     (m0 + m1) + (m2 + m3); lane (node, candidate) here walks the node's
+//     edges serially with four accumulators and folds the same way.
+// LDS = four bitmaps (nw rounded up to 4 words, cleared with 16-byte
+// stores) + per node: u16 prefix per word, qcap*(16|20) bytes, a 16-entry
+// edge table: 8 KB at K=5000 bf16 with qcap=64.  Measured in
+// profiles/r08_kfp_pack.md.
+
+#define KFP_NODES 4   // nodes per wave
+
+// bitmap words per node, rounded so the four bitmaps clear as uint4
+__host__ __device__ __forceinline__ int kfp_nwp(int K) {
+  return (((K + 31) >> 5) + 3) & ~3;
+}
+// bytes of one node's private region after the bitmaps (q4 = qcap rounded
+// up to 4): gacc, sfS f32 | ebs[16] u32 | (fp32: nval, fuS f32) | nidx, kS
+// u16 | pref[nwp] u16 | (bf16: nval, fuS u16); a multiple of 16
+__host__ __device__ __forceinline__ int kfp_node_bytes(bool bf16, int nwp,
+                                                       int q4) {
+  return (q4 * (bf16 ? 16 : 20) + KFP_DEG * 4 + nwp * 2 + 15) & ~15;
+}
+
+template <bool BF16>
+__global__ void __launch_bounds__(WAVE) kfp_sparse_t(
+    int K, const long long* __restrict__ indptr,
+    const int* __restrict__ indices, const float* __restrict__ sumF,
+    const int* __restrict__ order, const int* __restrict__ pos, int n_pack,
+    const long long* __restrict__ soffset, const int* __restrict__ sidx,
+    const float* __restrict__ sval, const int* __restrict__ scount,
+    const int* __restrict__ epre, const int* __restrict__ bound,
+    const long long* __restrict__ goffset,
+    int* __restrict__ gidx, float* __restrict__ gval,
+    int* __restrict__ gcount, double* __restrict__ llh,
+    const float* __restrict__ GGp, const float* __restrict__ ladder,
+    float* __restrict__ best, int n_ladder, int qcap, float alpha,
+    float min_p, float max_p, float min_f, float max_f) {
+  const int lane = threadIdx.x;
+  const int grp = lane >> 4;  // node of the quad
+  const int gl = lane & 15;   // lane in group == edge == candidate
+  const int nw = (K + 31) >> 5;
+  const int nwp = kfp_nwp(K);
+  const int q4 = (qcap + 3) & ~3;
+  const int slot = KFP_NODES * (int)blockIdx.x + grp;
+  const bool alive = slot < n_pack;
+  const int b = pos[alive ? slot : n_pack - 1];  // position, routed order
+  const int u = order[b];
+  const long long e0 = indptr[u];
+  const int deg_u = (int)(indptr[u + 1] - e0);
+  const int su_u = scount[u];
+  const int bnd = bound[u];
+  // routing sends only nodes with bound <= qcap and degree <= KFP_DEG
+  // here; anything else must not touch the slot arrays — it surfaces as a
+  // NaN llh instead
+  const bool fits = alive && deg_u <= KFP_DEG && bnd <= qcap && su_u <= bnd;
+  const int deg = fits ? deg_u : 0;
+  const int su = fits ? su_u : 0;
+  const int total = fits ? bnd - su_u : 0;  // staged entries
+  const long long offu = soffset[u];
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  u32* bmap = reinterpret_cast<u32*>(smem) + grp * nwp;
+  char* reg = smem + (size_t)KFP_NODES * nwp * 4 +
+              (size_t)grp * kfp_node_bytes(BF16, nwp, q4);
+  float* gacc = reinterpret_cast<float*>(reg);
+  float* sfS = gacc + q4;
+  u32* ebs = reinterpret_cast<u32*>(sfS + q4);
+  float* nval_f = reinterpret_cast<float*>(ebs + KFP_DEG);
+  float* fuS_f = nval_f + q4;
+  unsigned short* nidx = reinterpret_cast<unsigned short*>(
+      BF16 ? nval_f : fuS_f + q4);
+  unsigned short* kS = nidx + q4;
+  unsigned short* pref = kS + q4;
+  unsigned short* nval_h = pref + nwp;
+  unsigned short* fuS_h = nval_h + q4;
+
+  // lane e holds edge e of its node: (staging base << 16) | list length
+  // and the neighbour's list offset; 0 past the degree (an empty edge)
+  u32 bs_l = 0u;
+  long long off_l = 0;
+  if (gl < deg) {
+    bs_l = ((u32)epre[e0 + gl] << 16) |
+           (u32)epre_len(epre, e0 + gl, gl, deg, total);
+    off_l = soffset[indices[e0 + gl]];
+  }
+  ebs[gl] = bs_l;  // the trial phase indexes edges per lane
+  {
+    uint4* bm4 = reinterpret_cast<uint4*>(smem);  // 4 bitmaps = nwp uint4
+    for (int i = lane; i < nwp; i += WAVE) bm4[i] = make_uint4(0, 0, 0, 0);
+  }
+  int mdeg = max(deg, __shfl_xor(deg, 16, WAVE));
+  mdeg = max(mdeg, __shfl_xor(mdeg, 32, WAVE));  // the quad's largest
+  __syncthreads();
+
+  // phase 1: stage the neighbour lists edge by edge, OR support bits
+  for (int e = 0; e < mdeg; ++e) {
+    const u32 bs = __shfl(bs_l, e, 16);
+    const long long off = __shfl(off_l, e, 16);
+    const int base = (int)(bs >> 16);
+    const int sv = (int)(bs & 0xffffu);
+    for (int j = gl; j < sv; j += 16) {
+      const int k = sidx[off + j];
+      nidx[base + j] = (unsigned short)k;
+      if (BF16)
+        nval_h[base + j] = pack1_bf16_rne(sval[off + j]);
+      else
+        nval_f[base + j] = sval[off + j];
+      atomicOr(&bmap[k >> 5], 1u << (k & 31));
+    }
+  }
+  for (int j = gl; j < su; j += 16) {
+    const int k = sidx[offu + j];
+    atomicOr(&bmap[k >> 5], 1u << (k & 31));
+  }
+  __syncthreads();
+
+  // phase 1.5: bitmap scan over the group's 16 lanes -> sorted compact
+  // kS, per-word exclusive prefix, zeroed gacc/fuS slots
+  const int wchunk = (nw + 15) >> 4;
+  const int w0 = min(gl * wchunk, nw);
+  const int w1 = min(w0 + wchunk, nw);
+  int cnt = 0;
+  for (int wv = w0; wv < w1; ++wv) cnt += __popc(bmap[wv]);
+  int incl = cnt;
+#pragma unroll
+  for (int off = 1; off < 16; off <<= 1) {
+    const int v = __shfl_up(incl, off, 16);
+    if (gl >= off) incl += v;
+  }
+  const int ns = __shfl(incl, 15, 16);
+  if (cnt) {
+    int p_ = incl - cnt;
+    for (int wv = w0; wv < w1; ++wv) {
+      u32 bits = bmap[wv];
+      pref[wv] = (unsigned short)p_;
+      while (bits) {
+        const int bb = __ffs(bits) - 1;
+        bits &= bits - 1;
+        kS[p_] = (unsigned short)((wv << 5) + bb);
+        if (BF16)
+          fuS_h[p_] = 0;
+        else
+          fuS_f[p_] = 0.f;
+        gacc[p_] = 0.f;
+        ++p_;
+      }
+    }
+  }
+  __syncthreads();
+  auto rank_of = [&](int k) -> int {
+    const int wv = k >> 5;
+    return (int)pref[wv] + __popc(bmap[wv] & ((1u << (k & 31)) - 1u));
+  };
+  for (int j = gl; j < su; j += 16) {
+    const int p_ = rank_of(sidx[offu + j]);
+    if (BF16)
+      fuS_h[p_] = pack1_bf16_rne(sval[offu + j]);
+    else
+      fuS_f[p_] = sval[offu + j];
+  }
+  for (int i = gl; i < total; i += 16)
+    nidx[i] = (unsigned short)rank_of((int)nidx[i]);
+  __syncthreads();
+
+  // phase 2: the dots of all edges first (lane e keeps x_e), the
+  // transcendentals once over the edge lanes, then the scatter edge by
+  // edge in CSR order with w_e broadcast
+  float x = 0.f;
+  for (int e = 0; e < mdeg; ++e) {
+    const u32 bs = __shfl(bs_l, e, 16);
+    const int base = (int)(bs >> 16);
+    const int sv = (int)(bs & 0xffffu);
+    float part = 0.f;
+    for (int j = gl; j < sv; j += 16) {
+      const int p_ = (int)nidx[base + j];
+      const float fv = BF16 ? vget<true>(nval_h[base + j]) : nval_f[base + j];
+      const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
+      part += fu * fv;
+    }
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) part += __shfl_xor(part, off, WAVE);
+    if (gl == e) x = part;
+  }
+  const float p = clamp_p(__expf(-x), min_p, max_p);
+  const float w = 1.f / (1.f - p);
+  double llh_acc;
+  {
+    double le = 0.0;
+    if (gl < deg) le += (double)log1pf(-p) + (double)x;
+    double t = le + __shfl_down(le, 4, 16);
+    t += __shfl_down(le, 8, 16);
+    t += __shfl_down(le, 12, 16);          // lane q < 4: A_q
+    const double a = t + __shfl_down(t, 2, 16);  // A0 + A2 | A1 + A3
+    llh_acc = __shfl(a + __shfl_down(a, 1, 16), 0, 16);
+  }
+  for (int e = 0; e < mdeg; ++e) {
+    const u32 bs = __shfl(bs_l, e, 16);
+    const float wq = __shfl(w, e, 16);
+    const int bq = (int)(bs >> 16);
+    const int sq = (int)(bs & 0xffffu);
+    for (int j = gl; j < sq; j += 16) {
+      const int p_ = (int)nidx[bq + j];
+      const float fv = BF16 ? vget<true>(nval_h[bq + j]) : nval_f[bq + j];
+      gacc[p_] += wq * fv;
+    }
+  }
+  __syncthreads();
+
+  // phase 3: finalize g in place + write the global pools; the node sums
+  // keep KFW's 64-lane accumulation classes in four accumulators per lane
+  const long long go = goffset[b];
+  float gg_c[4] = {0.f, 0.f, 0.f, 0.f};
+  float fs_c[4] = {0.f, 0.f, 0.f, 0.f};
+  float ff_c[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int i0 = gl; i0 < ns; i0 += WAVE) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = i0 + 16 * q;
+      if (i < ns) {
+        const int k = (int)kS[i];
+        const float f = BF16 ? vget<true>(fuS_h[i]) : fuS_f[i];
+        const float sfk = sumF[k];
+        const float g = gacc[i] - sfk + f;
+        gacc[i] = g;
+        sfS[i] = sfk;
+        gidx[go + i] = k;
+        gval[go + i] = g;
+        gg_c[q] += g * g - sfk * sfk;
+        fs_c[q] = fmaf(f, sfk, fs_c[q]);
+        ff_c[q] = fmaf(f, f, ff_c[q]);
+      }
+    }
+  }
+  float gg_p = (gg_c[0] + gg_c[2]) + (gg_c[1] + gg_c[3]);
+  float fs_p = (fs_c[0] + fs_c[2]) + (fs_c[1] + fs_c[3]);
+  float ff_p = (ff_c[0] + ff_c[2]) + (ff_c[1] + ff_c[3]);
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) {
+    gg_p += __shfl_xor(gg_p, off, WAVE);
+    fs_p += __shfl_xor(fs_p, off, WAVE);
+    ff_p += __shfl_xor(ff_p, off, WAVE);
+  }
+  const double llh_base = llh_acc + (double)(-fs_p) + (double)ff_p;
+  const float gg = gg_p + GGp[0];
+  if (gl == 0 && alive) {
+    gcount[b] = ns;
+    llh[u] = fits ? llh_base : (double)__builtin_nanf("");
+  }
+  __syncthreads();
+
+  // phase 4: 16-candidate trials, lane (node, candidate) walks the node's
+  // edges serially; accumulator q takes edges / slots = q (mod 4)
+  const bool live = gl < n_ladder;
+  const float sj = live ? ladder[gl] : 0.f;
+  double m[4] = {0.0, 0.0, 0.0, 0.0};
+  float nt[4] = {0.f, 0.f, 0.f, 0.f};
+  if (live) {
+    for (int et = 0; et < deg; et += 4) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (et + q < deg) {
+          const u32 bs = ebs[et + q];
+          const int base = (int)(bs >> 16);
+          const int sv = (int)(bs & 0xffffu);
+          float xt = 0.f;
+          for (int t = 0; t < sv; ++t) {
+            const int p_ = (int)nidx[base + t];
+            const float fv =
+                BF16 ? vget<true>(nval_h[base + t]) : nval_f[base + t];
+            const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
+            const float c =
+                __builtin_amdgcn_fmed3f(fmaf(sj, gacc[p_], fu), min_f, max_f);
+            xt = fmaf(c, fv, xt);
+          }
+          const float pt = clamp_p(__expf(-xt), min_p, max_p);
+          m[q] += (double)log1pf(-pt) + (double)xt;
+        }
+      }
+    }
+    for (int i0 = 0; i0 < ns; i0 += 4) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int i = i0 + q;
+        if (i < ns) {
+          const float fu = BF16 ? vget<true>(fuS_h[i]) : fuS_f[i];
+          const float c =
+              __builtin_amdgcn_fmed3f(fmaf(sj, gacc[i], fu), min_f, max_f);
+          nt[q] = fmaf(c, fu - sfS[i], nt[q]);
+        }
+      }
+    }
+  }
+  const double myllh = (m[0] + m[1]) + (m[2] + m[3]);
+  const float mynt = (nt[0] + nt[1]) + (nt[2] + nt[3]);
+  const bool ok = live && (myllh + (double)mynt >=
+                           llh_base + (double)(alpha * sj * gg));
+  const unsigned long long bal = (__ballot(ok) >> (grp * 16)) & 0xffffull;
+  const float spick = __shfl(sj, bal ? __ffsll(bal) - 1 : 0, 16);
+  if (gl == 0 && alive) best[u] = bal ? spick : 0.f;
 }
 
 // K3S also REWRITES the committed row's persistent support list
@@ -4208,7 +4576,8 @@ extern "C" long long kfw_lds_bytes(int bf16, int K, int wcap) {
 
 extern "C" void launch_kfw(int bf16, const long long* indptr,
                            const int* indices, const float* sumF,
-                           const int* order, int blk0, int n_blocks,
+                           const int* order, int blk0, const int* pos,
+                           int n_blocks,
                            const long long* soffset, const int* sidx,
                            const float* sval, const int* scount,
                            const int* epre, const int* bound,
@@ -4226,16 +4595,62 @@ extern "C" void launch_kfw(int bf16, const long long* indptr,
   if (bf16) {
     allow_large_lds((const void*)&kfw_sparse_t<true>, lds);
     hipLaunchKernelGGL((kfw_sparse_t<true>), dim3(n_blocks), dim3(WAVE), lds,
-                       stream, K, indptr, indices, sumF, order, blk0,
+                       stream, K, indptr, indices, sumF, order, blk0, pos,
                        soffset, sidx, sval, scount, epre, bound, goffset, gidx,
                        gval, gcount, llh, GGp, ladder, best, n_ladder, wcap,
                        alpha, min_p, max_p, min_f, max_f);
   } else {
     allow_large_lds((const void*)&kfw_sparse_t<false>, lds);
     hipLaunchKernelGGL((kfw_sparse_t<false>), dim3(n_blocks), dim3(WAVE), lds,
-                       stream, K, indptr, indices, sumF, order, blk0,
+                       stream, K, indptr, indices, sumF, order, blk0, pos,
                        soffset, sidx, sval, scount, epre, bound, goffset, gidx,
                        gval, gcount, llh, GGp, ladder, best, n_ladder, wcap,
+                       alpha, min_p, max_p, min_f, max_f);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// KFP LDS bytes for (K, qcap): four bitmaps + per node (u16 prefix +
+// qcap*(16|20) + the 16-entry edge table).  Exposed so the host clamps
+// qcap to the workgroup budget.
+extern "C" long long kfp_lds_bytes(int bf16, int K, int qcap) {
+  const int nwp = kfp_nwp(K);
+  return (long long)KFP_NODES *
+         (nwp * 4 + kfp_node_bytes(bf16 != 0, nwp, (qcap + 3) & ~3));
+}
+
+extern "C" int kfp_deg() { return KFP_DEG; }
+
+// KFP over the pack positions pos[0 .. n_pack), four per workgroup
+extern "C" void launch_kfp(int bf16, const long long* indptr,
+                           const int* indices, const float* sumF,
+                           const int* order, const int* pos, int n_pack,
+                           const long long* soffset, const int* sidx,
+                           const float* sval, const int* scount,
+                           const int* epre, const int* bound,
+                           const long long* goffset,
+                           int* gidx, float* gval, int* gcount, double* llh,
+                           const float* GGp, const float* ladder,
+                           float* best, int n_ladder, int qcap, int K,
+                           float alpha, float min_p, float max_p,
+                           float min_f, float max_f, hipStream_t stream) {
+  if (n_pack == 0) return;
+  if (n_ladder > 16) throw std::runtime_error("ladder length > 16 unsupported");
+  const size_t lds = (size_t)kfp_lds_bytes(bf16, K, qcap);
+  if (qcap <= 0 || qcap > 65535 || lds > 64 * 1024)
+    throw std::runtime_error("KFP: qcap exceeds the workgroup LDS budget");
+  const int grid = (n_pack + KFP_NODES - 1) / KFP_NODES;
+  if (bf16) {
+    hipLaunchKernelGGL((kfp_sparse_t<true>), dim3(grid), dim3(WAVE), lds,
+                       stream, K, indptr, indices, sumF, order, pos, n_pack,
+                       soffset, sidx, sval, scount, epre, bound, goffset, gidx,
+                       gval, gcount, llh, GGp, ladder, best, n_ladder, qcap,
+                       alpha, min_p, max_p, min_f, max_f);
+  } else {
+    hipLaunchKernelGGL((kfp_sparse_t<false>), dim3(grid), dim3(WAVE), lds,
+                       stream, K, indptr, indices, sumF, order, pos, n_pack,
+                       soffset, sidx, sval, scount, epre, bound, goffset, gidx,
+                       gval, gcount, llh, GGp, ladder, best, n_ladder, qcap,
                        alpha, min_p, max_p, min_f, max_f);
   }
   HIP_CHECK(hipGetLastError());
@@ -4331,13 +4746,17 @@ extern "C" int route_tile() { return RT_TILE; }
 
 // Routing: bounds + classes, tile scan (+ GG), stable placement.  The
 // three class totals are left in `totals` (device) for the caller's one
-// host read.  tcount/tbase hold 3 ints per tile.
+// host read.  tcount/tbase hold 3 ints per tile.  pscr (nullable, with
+// wsplit): [3 ints per tile: packable count, ballot lo, hi | a base per
+// tile | n_pack] = 4 * tiles + 1 ints, for the packed / single split of
+// the wave class.
 extern "C" void launch_route(const long long* indptr, const int* indices,
                              const int* scount, const int* order,
                              int n_local, int cap, int wcap,
                              const float* sumF, int K, int* epre, int* bound,
                              unsigned char* cls, int* tcount, int* tbase,
                              int* totals, float* GG, int* by_class,
+                             int qcap, int* pscr, int* wsplit,
                              hipStream_t stream) {
   static_assert(RT_TILE == WAVE && RT_TILE % (BLOCK / RT_GRP) == 0,
                 "one wave places a tile; groups cover it in whole rounds");
@@ -4345,13 +4764,15 @@ extern "C" void launch_route(const long long* indptr, const int* indices,
   if (n_tiles > 0)
     hipLaunchKernelGGL(kr_bounds, dim3(n_tiles), dim3(BLOCK), 0, stream,
                        indptr, indices, scount, order, n_local, cap, wcap,
-                       epre, bound, cls, tcount);
+                       epre, bound, cls, tcount, qcap, pscr);
   hipLaunchKernelGGL(kr_scan, dim3(1), dim3(RT_SCAN), 0, stream, tcount,
-                     n_tiles, tbase, totals, sumF, K, GG);
+                     n_tiles, tbase, totals, sumF, K, GG, pscr,
+                     pscr ? pscr + 3 * n_tiles : nullptr);
   if (n_tiles > 0)
     hipLaunchKernelGGL(kr_place, dim3((n_tiles + NWAVE - 1) / NWAVE),
                        dim3(BLOCK), 0, stream, order, cls, tbase, totals,
-                       n_local, n_tiles, by_class);
+                       n_local, n_tiles, by_class, pscr,
+                       pscr ? pscr + 3 * n_tiles : nullptr, wsplit);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -397,18 +397,51 @@ extern "C" void launch_kfs(const void*, int, const long long*, const int*,
                            float*, int, int, int, float, float, float,
                            float, float, hipStream_t);
 extern "C" void launch_kfw(int, const long long*, const int*, const float*,
-                           const int*, int, int, const long long*,
+                           const int*, int, const int*, int, const long long*,
                            const int*, const float*, const int*,
                            const int*, const int*, const long long*, int*,
                            float*, int*, double*, const float*, const float*,
                            float*, int, int, int, float, float, float,
                            float, float, hipStream_t);
 extern "C" long long kfw_lds_bytes(int, int, int);
+extern "C" long long kfp_lds_bytes(int, int, int);
+extern "C" void launch_kfp(int, const long long*, const int*, const float*,
+                           const int*, const int*, int, const long long*,
+                           const int*, const float*, const int*,
+                           const int*, const int*, const long long*, int*,
+                           float*, int*, double*, const float*, const float*,
+                           float*, int, int, int, float, float, float,
+                           float, float, hipStream_t);
 extern "C" void launch_k3s(void*, int, const int*, int, int,
                            const long long*, const int*, const float*,
                            const int*, const float*, const long long*, int*,
                            float*, int*, unsigned char*, int, int, float,
                            float, hipStream_t);
+
+// A side stream per device with its fork / join events.  The single
+// (one wave per node) part of a packed wave class holds the widest nodes
+// of the class: a few thousand long waves that fill a fraction of the
+// device.  Alone after the packed launch they cost their full latency;
+// on the side stream they run next to it.
+struct WaveSide {
+  hipStream_t stream = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+};
+static WaveSide& wave_side() {
+  static WaveSide per_dev[64];
+  int dev = 0;
+  TORCH_CHECK(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64);
+  WaveSide& w = per_dev[dev];
+  if (!w.stream) {
+    TORCH_CHECK(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking) ==
+                hipSuccess);
+    TORCH_CHECK(hipEventCreateWithFlags(&w.fork, hipEventDisableTiming) ==
+                hipSuccess);
+    TORCH_CHECK(hipEventCreateWithFlags(&w.join, hipEventDisableTiming) ==
+                hipSuccess);
+  }
+  return w;
+}
 
 static const long long* i64p(const torch::Tensor& t) {
   return reinterpret_cast<const long long*>(t.data_ptr<int64_t>());
@@ -462,10 +495,14 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
                   torch::Tensor llh, torch::Tensor GG, torch::Tensor ladder,
                   torch::Tensor best, int64_t cap, double alpha,
                   double min_p, double max_p, double min_f, double max_f,
-                  int64_t n_block, int64_t wcap) {
+                  int64_t n_block, int64_t wcap, int64_t qcap,
+                  std::optional<torch::Tensor> wsplit, int64_t n_pack) {
   // order[:n_block] runs the block kernel (KFS), order[n_block:] the
   // one-wave-per-node kernel (KFW, bound <= wcap); pools and gcount are
-  // indexed by position in `order` for both
+  // indexed by position in `order` for both.  With qcap > 0 and the
+  // routing's wsplit, the wave class runs as two launches: the pack
+  // positions wsplit[:n_pack] four nodes per wave (KFP), the rest
+  // wsplit[n_pack:n_wave] one wave per node (KFW).
   CHECK_F(F);
   CHECK_IN(indptr, torch::kInt64);
   CHECK_IN(indices, torch::kInt32);
@@ -493,11 +530,39 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
   const int n_wave = n_blocks - (int)n_block;
   TORCH_CHECK(n_wave == 0 || (wcap > 0 && wcap <= cap),
               "wave class needs 0 < wcap <= cap");
-  if (n_wave > 0)
+  const bool packed = qcap > 0 && wsplit.has_value();
+  const int* wsp = nullptr;
+  hipStream_t main_s = current_stream();
+  hipStream_t wave_s = main_s;  // where the single-wave launch goes
+  WaveSide* side = nullptr;
+  if (packed) {
+    CHECK_IN((*wsplit), torch::kInt32);
+    TORCH_CHECK(qcap <= wcap, "packed wave class needs qcap <= wcap <= cap");
+    TORCH_CHECK(n_pack >= 0 && n_pack <= n_wave, "n_pack out of range");
+    TORCH_CHECK(wsplit->dim() == 1 && wsplit->size(0) >= n_wave,
+                "wsplit must hold the wave class");
+    TORCH_CHECK(kfp_lds_bytes(is_bf16(F) ? 1 : 0, (int)F.size(1), (int)qcap) <=
+                    64 * 1024,
+                "qcap exceeds the packed kernel's LDS budget");
+    wsp = wsplit->data_ptr<int>();
+    if (n_pack > 0 && n_pack < n_wave) {
+      // both parts non-empty: the single part forks to the side stream
+      // (it only reads what the main stream has finished writing, and
+      // writes positions no other launch of this call touches)
+      side = &wave_side();
+      TORCH_CHECK(hipEventRecord(side->fork, main_s) == hipSuccess);
+      TORCH_CHECK(hipStreamWaitEvent(side->stream, side->fork, 0) ==
+                  hipSuccess);
+      wave_s = side->stream;
+    }
+  }
+  const int w_first = packed ? (int)n_pack : (int)n_block;
+  const int w_count = packed ? n_wave - (int)n_pack : n_wave;
+  if (w_count > 0)
     launch_kfw(is_bf16(F) ? 1 : 0,
                reinterpret_cast<const long long*>(indptr.data_ptr<int64_t>()),
                indices.data_ptr<int>(), sumF.data_ptr<float>(),
-               order.data_ptr<int>(), (int)n_block, n_wave, i64p(soffset),
+               order.data_ptr<int>(), w_first, wsp, w_count, i64p(soffset),
                sidx.data_ptr<int>(), sval.data_ptr<float>(),
                scount.data_ptr<int>(), epre.data_ptr<int>(),
                bound.data_ptr<int>(), i64p(goffset),
@@ -506,7 +571,22 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
                GG.data_ptr<float>(), ladder.data_ptr<float>(),
                best.data_ptr<float>(), (int)ladder.size(0), (int)wcap,
                (int)F.size(1), (float)alpha, (float)min_p, (float)max_p,
-               (float)min_f, (float)max_f, current_stream());
+               (float)min_f, (float)max_f, wave_s);
+  if (side) TORCH_CHECK(hipEventRecord(side->join, wave_s) == hipSuccess);
+  if (packed)
+    launch_kfp(is_bf16(F) ? 1 : 0, i64p(indptr), indices.data_ptr<int>(),
+               sumF.data_ptr<float>(), order.data_ptr<int>(), wsp,
+               (int)n_pack, i64p(soffset), sidx.data_ptr<int>(),
+               sval.data_ptr<float>(), scount.data_ptr<int>(),
+               epre.data_ptr<int>(), bound.data_ptr<int>(), i64p(goffset),
+               gidx.data_ptr<int>(), gval.data_ptr<float>(),
+               gcount.data_ptr<int>(), llh.data_ptr<double>(),
+               GG.data_ptr<float>(), ladder.data_ptr<float>(),
+               best.data_ptr<float>(), (int)ladder.size(0), (int)qcap,
+               (int)F.size(1), (float)alpha, (float)min_p, (float)max_p,
+               (float)min_f, (float)max_f, main_s);
+  if (side)
+    TORCH_CHECK(hipStreamWaitEvent(main_s, side->join, 0) == hipSuccess);
   launch_kfs(F.data_ptr(), is_bf16(F) ? 1 : 0,
              reinterpret_cast<const long long*>(indptr.data_ptr<int64_t>()),
              indices.data_ptr<int>(), sumF.data_ptr<float>(),
@@ -631,7 +711,7 @@ extern "C" int route_tile();
 extern "C" void launch_route(const long long*, const int*, const int*,
                              const int*, int, int, int, const float*, int,
                              int*, int*, unsigned char*, int*, int*, int*,
-                             float*, int*, hipStream_t);
+                             float*, int*, int, int*, int*, hipStream_t);
 
 // Stage 2 of the column-sum refresh: out[k] = sum_s partials[s, k] in a
 // fixed order (see kcs_stage2).
@@ -650,12 +730,20 @@ void colsum_stage2(torch::Tensor partials, torch::Tensor out) {
 // [nnz], bound [n_local], by_class [n_local] = [block | wave | dense] and
 // GG [1]; returns the three class sizes (the sweep's routing host sync).
 // cls/tcount/tbase/totals are scratch the caller keeps allocated.
+// With qcap / wsplit [n_local] / pscr [4 * tiles + 1] given, the same three
+// launches also split the wave class for the packed kernel (KFP):
+// wsplit[:n_pack] = pack positions (n_block + rank in the wave class) of
+// the nodes with bound <= qcap and degree <= 16, wsplit[n_pack:n_wave]
+// those of the others, both in launch order; n_pack is returned as a
+// fourth value from the same host sync.  Nothing else changes.
 std::vector<int64_t> sparse_route(
     torch::Tensor indptr, torch::Tensor indices, torch::Tensor scount,
     torch::Tensor order, torch::Tensor sumF, int64_t cap, int64_t wcap,
     torch::Tensor epre, torch::Tensor bound, torch::Tensor cls,
     torch::Tensor tcount, torch::Tensor tbase, torch::Tensor totals,
-    torch::Tensor GG, torch::Tensor by_class) {
+    torch::Tensor GG, torch::Tensor by_class,
+    std::optional<int64_t> qcap, std::optional<torch::Tensor> wsplit,
+    std::optional<torch::Tensor> pscr) {
   CHECK_IN(indptr, torch::kInt64);
   CHECK_IN(indices, torch::kInt32);
   CHECK_IN(scount, torch::kInt32);
@@ -679,6 +767,24 @@ std::vector<int64_t> sparse_route(
               totals.size(0) >= 3 && GG.size(0) >= 1);
   TORCH_CHECK(cap >= 0 && cap < (1 << 29) && wcap >= 0 && wcap <= cap,
               "need 0 <= wcap <= cap < 2^29");
+  const bool split = wsplit.has_value();
+  TORCH_CHECK(split == qcap.has_value() && split == pscr.has_value(),
+              "qcap, wsplit and pscr go together");
+  int* wsp = nullptr;
+  int* psp = nullptr;
+  int q = 0;
+  if (split) {
+    CHECK_IN((*wsplit), torch::kInt32);
+    CHECK_IN((*pscr), torch::kInt32);
+    q = (int)*qcap;
+    TORCH_CHECK(*qcap >= 0 && *qcap <= wcap, "need 0 <= qcap <= wcap");
+    TORCH_CHECK(wsplit->dim() == 1 && wsplit->size(0) == n_local,
+                "wsplit must be int32 [n_local]");
+    TORCH_CHECK(pscr->dim() == 1 && pscr->size(0) >= 4 * n_tiles + 1,
+                "pscr must hold 4 ints per routing tile + 1");
+    wsp = wsplit->data_ptr<int>();
+    psp = pscr->data_ptr<int>();
+  }
   hipStream_t stream = current_stream();
   launch_route(i64p(indptr), indices.data_ptr<int>(), scount.data_ptr<int>(),
                order.data_ptr<int>(), (int)n_local, (int)cap, (int)wcap,
@@ -686,11 +792,16 @@ std::vector<int64_t> sparse_route(
                epre.data_ptr<int>(), bound.data_ptr<int>(),
                cls.data_ptr<uint8_t>(), tcount.data_ptr<int>(),
                tbase.data_ptr<int>(), totals.data_ptr<int>(),
-               GG.data_ptr<float>(), by_class.data_ptr<int>(), stream);
-  int h[3] = {0, 0, 0};
-  TORCH_CHECK(hipMemcpyAsync(h, totals.data_ptr<int>(), sizeof(h),
+               GG.data_ptr<float>(), by_class.data_ptr<int>(), q, psp, wsp,
+               stream);
+  int h[4] = {0, 0, 0, 0};
+  TORCH_CHECK(hipMemcpyAsync(h, totals.data_ptr<int>(), 3 * sizeof(int),
                              hipMemcpyDeviceToHost, stream) == hipSuccess);
+  if (split)
+    TORCH_CHECK(hipMemcpyAsync(h + 3, psp + 4 * n_tiles, sizeof(int),
+                               hipMemcpyDeviceToHost, stream) == hipSuccess);
   TORCH_CHECK(hipStreamSynchronize(stream) == hipSuccess);
+  if (split) return {h[0], h[1], h[2], h[3]};
   return {h[0], h[1], h[2]};
 }
 
@@ -871,9 +982,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sval"), py::arg("cap"), py::arg("fill"), py::arg("dirty"),
         py::arg("rows") = py::none());
   m.def("sparse_fused", &sparse_fused,
-        "KFS/KFW: fused compact gradient + 16-candidate Armijo for routed "
+        "KFS/KFW/KFP: fused compact gradient + 16-candidate Armijo for routed "
         "nodes (LDS bitmap active sets); order[:n_block] one block per "
-        "node, order[n_block:] one wave per node");
+        "node, order[n_block:] one wave per node, or four per wave for the "
+        "pack positions wsplit[:n_pack] when qcap > 0",
+        py::arg("F"), py::arg("indptr"), py::arg("indices"), py::arg("sumF"),
+        py::arg("order"), py::arg("soffset"), py::arg("sidx"),
+        py::arg("sval"), py::arg("scount"), py::arg("epre"),
+        py::arg("bound"), py::arg("goffset"), py::arg("gidx"),
+        py::arg("gval"), py::arg("gcount"), py::arg("llh"), py::arg("GG"),
+        py::arg("ladder"), py::arg("best"), py::arg("cap"), py::arg("alpha"),
+        py::arg("min_p"), py::arg("max_p"), py::arg("min_f"),
+        py::arg("max_f"), py::arg("n_block"), py::arg("wcap"),
+        py::arg("qcap") = 0, py::arg("wsplit") = py::none(),
+        py::arg("n_pack") = 0);
+  m.def("sparse_pack_lds_bytes",
+        [](bool bf16, int64_t K, int64_t qcap) {
+          return (int64_t)kfp_lds_bytes(bf16 ? 1 : 0, (int)K, (int)qcap);
+        },
+        "KFP dynamic LDS bytes at (dtype, padded K, qcap)");
   m.def("sparse_wave_lds_bytes",
         [](bool bf16, int64_t K, int64_t wcap) {
           return (int64_t)kfw_lds_bytes(bf16 ? 1 : 0, (int)K, (int)wcap);
@@ -885,7 +1012,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fixed-order sum of the [n_stripes, K] column partials into out[K]");
   m.def("sparse_route", &sparse_route,
         "routing: node-local support prefix, bounds, classes and the stable "
-        "[block | wave | dense] order; returns the three class sizes");
+        "[block | wave | dense] order; returns the three class sizes (and "
+        "n_pack when the packed split is requested)",
+        py::arg("indptr"), py::arg("indices"), py::arg("scount"),
+        py::arg("order"), py::arg("sumF"), py::arg("cap"), py::arg("wcap"),
+        py::arg("epre"), py::arg("bound"), py::arg("cls"), py::arg("tcount"),
+        py::arg("tbase"), py::arg("totals"), py::arg("GG"),
+        py::arg("by_class"), py::arg("qcap") = py::none(),
+        py::arg("wsplit") = py::none(), py::arg("pscr") = py::none());
   m.def("sparse_route_tile", []() { return (int64_t)route_tile(); },
         "launch-order positions per routing tile");
   m.def("sparse_commit", &sparse_commit,

@@ -281,6 +281,9 @@ def sparse_sweep_part(
     n_block: int = None,
     wcap: int = 0,
     GG: torch.Tensor = None,
+    qcap: int = 0,
+    wsplit: torch.Tensor = None,
+    n_pack: int = 0,
 ):
     """KFS/KFW for the routed (sparse) nodes: the compact gradient pools,
     llh per node, and the Armijo best step.  ``order_sparse[:n_block]``
@@ -291,7 +294,10 @@ def sparse_sweep_part(
     node positions; returns the commit pack for K3S.  ``epre`` (int32
     [nnz], node-local exclusive support prefix) and ``bound`` (int32
     [n_local]) come from the routing pass, as does ``GG`` = Σ sumF²
-    (computed here when not given)."""
+    (computed here when not given).  With ``qcap > 0`` and the routing's
+    ``wsplit``, the wave class runs as two launches: the pack positions
+    ``wsplit[:n_pack]`` four nodes per wave (KFP), the rest one wave per
+    node; the outputs are bitwise the same either way."""
     ext = ensure_loaded()
     dev = F.device
     n_s = int(order_sparse.numel())
@@ -308,7 +314,7 @@ def sparse_sweep_part(
         F, indptr, indices, sumF, order_sparse, soffset, sidx, sval, scount,
         epre, bound, goffset, gidx, gval, gcount, llh_out, GG, _ladder(cfg, dev),
         best_out, cap, cfg.alpha, cfg.min_p, cfg.max_p, cfg.min_f, cfg.max_f,
-        int(n_block), int(wcap),
+        int(n_block), int(wcap), int(qcap), wsplit, int(n_pack),
     )
     return {
         "order": order_sparse,

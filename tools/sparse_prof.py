@@ -67,14 +67,16 @@ def main():
         carry, llh, _ = tr.pipelined_sweep(carry)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
-    routed = None
+    routed = n_pack = None
     if carry[2] is not None:
         routed = int(carry[2]["order"].numel())
+        n_pack = carry[2].get("n_pack")  # packed wave kernel's share
     print(json.dumps({
         "mode": args.mode, "k": args.k, "dtype": args.dtype,
         "ms_per_sweep": round(dt * 1000.0, 3),
         "edges_per_s": g.num_directed_edges / dt,
         "f_nnz_frac": round(nnz, 5), "routed_nodes": routed,
+        "n_pack": n_pack,
         "n_local": tr.state.n_local, "llh": llh,
     }), flush=True)
 
