@@ -568,6 +568,15 @@ class ShardState:
         return max(0, min(q, self.sparse_wcap, fit))
 
     @property
+    def sparse_skip(self) -> bool:
+        """Run the KFW/KFP builds in which an edge with an empty neighbour
+        list, and a node with an empty active set, cost a lane-parallel
+        test instead of a walk.  Every output is bitwise the same;
+        BIGCLAM_SPARSE_SKIP=0 selects the builds without it, the A/B
+        reference of the tests and the benchmark."""
+        return os.environ.get("BIGCLAM_SPARSE_SKIP", "1") != "0"
+
+    @property
     def sparse_allowed(self) -> bool:
         """Active-column sweep (docs/sparse_sweep_design.md): exact
         per-node routing by active-set bound; pays off once F sparsifies
@@ -814,7 +823,7 @@ class ShardState:
             state_pools=(self._sp_gidx, self._sp_gval),
             n_block=n_blk, wcap=wcap, GG=GG,
             qcap=qcap if wsplit is not None else 0, wsplit=wsplit,
-            n_pack=n_pack,
+            n_pack=n_pack, skip=self.sparse_skip,
         )
         pack["n_block"] = n_blk  # order[:n_block] block class, rest wave
         pack["wcap"] = wcap

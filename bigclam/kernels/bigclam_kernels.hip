@@ -3164,7 +3164,25 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
 
 #define KFW_ECAP 64
 
-template <bool BF16>
+// The llh term and every trial term of an edge whose neighbour list is
+// empty: the dot is 0.f whatever the step, so the term is this constant.
+// The same expression the edge loops evaluate at x = 0.f, on the same
+// inputs — bitwise the value they would recompute.
+__device__ __forceinline__ double empty_edge_term(float min_p, float max_p) {
+  const float x = 0.f;
+  return (double)log1pf(-clamp_p(__expf(-x), min_p, max_p)) + (double)x;
+}
+
+// SKIP (KFW and KFP): an edge with an empty neighbour list costs a
+// lane-parallel test, not a walk.  Edge tables live in lanes (lane e =
+// edge e, 64 per chunk in KFW, 16 per node in KFP); a ballot marks the
+// non-empty edges and staging, dots and scatter loop over its set bits
+// in ascending CSR order; an empty edge adds empty_edge_term() where the
+// term would be recomputed, at the same place in the same chain of
+// double additions.  A node (KFP: a quad) with nothing staged and no own
+// support skips the bitmap passes altogether.  SKIP = false is the
+// kernel without any of this (BIGCLAM_SPARSE_SKIP=0, the A/B reference).
+template <bool BF16, bool SKIP>
 __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
     int K, const long long* __restrict__ indptr,
     const int* __restrict__ indices, const float* __restrict__ sumF,
@@ -3206,104 +3224,222 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
 
   // edge table: (staging base << 16) | list length, from the node-local
   // prefix
-  const int total = bound[u] - scount[u];  // staged entries
-  if (lane < deg)  // KFW_ECAP == WAVE: one pass
-    ebs[lane] = ((u32)epre[e0 + lane] << 16) |
-                (u32)epre_len(epre, e0 + lane, lane, deg, total);
-  for (int i = lane; i < nw; i += WAVE) bmap[i] = 0u;
-  __syncthreads();
+  const int bnd = bound[u];
+  const int total = bnd - scount[u];  // staged entries
+  // SKIP: nothing staged and no own support — the active set is empty,
+  // every edge term is c0: no bitmap pass, no rank, no phase-3 loop
+  const bool quick = SKIP && bnd == 0;
+  const double c0 = empty_edge_term(min_p, max_p);
+  u32 bs0 = 0u;  // SKIP: lane e keeps edge e's entry (first 64 edges)
+  if (!quick) {
+    if (lane < deg) {  // KFW_ECAP == WAVE: one pass
+      bs0 = ((u32)epre[e0 + lane] << 16) |
+            (u32)epre_len(epre, e0 + lane, lane, deg, total);
+      if (!SKIP) ebs[lane] = bs0;
+    }
+    for (int i = lane; i < nw; i += WAVE) bmap[i] = 0u;
+    __syncthreads();
+  }
   auto edge_bs = [&](int i) -> u32 {
     if (i < KFW_ECAP) return ebs[i];
     return ((u32)epre[e0 + i] << 16) |
            (u32)epre_len(epre, e0 + i, i, deg, total);
   };
+  // SKIP: the entries of edges c .. c+63, one per lane (one coalesced
+  // epre read per 64 edges past the first chunk); 0 past the degree
+  auto chunk_bs = [&](int c) -> u32 {
+    if (c == 0) return bs0;
+    const int i = c + lane;
+    return i < deg ? ((u32)epre[e0 + i] << 16) |
+                         (u32)epre_len(epre, e0 + i, i, deg, total)
+                   : 0u;
+  };
 
   // phase 1: stage neighbour lists, 4 edges at a time (16 lanes per
   // edge), OR support bits
-  for (int et = 0; et < deg; et += 4) {
-    const int ei = et + grp;
-    if (ei < deg) {
-      const u32 bs = edge_bs(ei);
-      const int base = (int)(bs >> 16);
-      const int sv = (int)(bs & 0xffffu);
-      if (sv) {
-        const long long off = soffset[indices[e0 + ei]];
-        for (int j = gl; j < sv; j += 16) {
-          const int k = sidx[off + j];
-          nidx[base + j] = (unsigned short)k;
-          if (BF16)
-            nval_h[base + j] = pack1_bf16_rne(sval[off + j]);
-          else
-            nval_f[base + j] = sval[off + j];
-          atomicOr(&bmap[k >> 5], 1u << (k & 31));
-        }
+  auto stage_edge = [&](int ei, u32 bs) {
+    const int base = (int)(bs >> 16);
+    const int sv = (int)(bs & 0xffffu);
+    if (sv) {
+      const long long off = soffset[indices[e0 + ei]];
+      for (int j = gl; j < sv; j += 16) {
+        const int k = sidx[off + j];
+        nidx[base + j] = (unsigned short)k;
+        if (BF16)
+          nval_h[base + j] = pack1_bf16_rne(sval[off + j]);
+        else
+          nval_f[base + j] = sval[off + j];
+        atomicOr(&bmap[k >> 5], 1u << (k & 31));
       }
+    }
+  };
+  if (SKIP) {
+    // the non-empty edges of each chunk, four set bits at a time
+    for (int c = 0; c < deg && !quick; c += WAVE) {
+      const u32 bs_l = chunk_bs(c);
+      unsigned long long m = __ballot((bs_l & 0xffffu) != 0u);
+      while (m) {
+        int mine = -1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (m) {
+            if (grp == r) mine = __ffsll(m) - 1;
+            m &= m - 1;
+          }
+        }
+        const u32 bs = __shfl(bs_l, mine < 0 ? 0 : mine, WAVE);
+        if (mine >= 0) stage_edge(c + mine, bs);
+      }
+    }
+  } else {
+    for (int et = 0; et < deg; et += 4) {
+      const int ei = et + grp;
+      if (ei < deg) stage_edge(ei, edge_bs(ei));
     }
   }
   const long long offu = soffset[u];
   const int su = scount[u];
-  for (int j = lane; j < su; j += WAVE) {
-    const int k = sidx[offu + j];
-    atomicOr(&bmap[k >> 5], 1u << (k & 31));
-  }
-  __syncthreads();
+  int ns = 0;
+  if (!quick) {
+    for (int j = lane; j < su; j += WAVE) {
+      const int k = sidx[offu + j];
+      atomicOr(&bmap[k >> 5], 1u << (k & 31));
+    }
+    __syncthreads();
 
-  // phase 1.5: bitmap scan -> sorted compact kS, per-word exclusive
-  // prefix, zeroed gacc/fuS slots
-  const int wchunk = (nw + WAVE - 1) / WAVE;
-  const int w0 = min(lane * wchunk, nw);
-  const int w1 = min(w0 + wchunk, nw);
-  int cnt = 0;
-  for (int wv = w0; wv < w1; ++wv) cnt += __popc(bmap[wv]);
-  int incl = cnt;
+    // phase 1.5: bitmap scan -> sorted compact kS, per-word exclusive
+    // prefix, zeroed gacc/fuS slots
+    const int wchunk = (nw + WAVE - 1) / WAVE;
+    const int w0 = min(lane * wchunk, nw);
+    const int w1 = min(w0 + wchunk, nw);
+    int cnt = 0;
+    for (int wv = w0; wv < w1; ++wv) cnt += __popc(bmap[wv]);
+    int incl = cnt;
 #pragma unroll
-  for (int off = 1; off < WAVE; off <<= 1) {
-    const int v = __shfl_up(incl, off, WAVE);
-    if (lane >= off) incl += v;
-  }
-  const int ns = __shfl(incl, WAVE - 1, WAVE);
-  {
-    int pos = incl - cnt;
-    for (int wv = w0; wv < w1; ++wv) {
-      u32 bits = bmap[wv];
-      pref[wv] = (unsigned short)pos;
-      while (bits) {
-        const int bb = __ffs(bits) - 1;
-        bits &= bits - 1;
-        kS[pos] = (unsigned short)((wv << 5) + bb);
-        if (BF16)
-          fuS_h[pos] = 0;
-        else
-          fuS_f[pos] = 0.f;
-        gacc[pos] = 0.f;
-        ++pos;
+    for (int off = 1; off < WAVE; off <<= 1) {
+      const int v = __shfl_up(incl, off, WAVE);
+      if (lane >= off) incl += v;
+    }
+    ns = __shfl(incl, WAVE - 1, WAVE);
+    {
+      int pos = incl - cnt;
+      for (int wv = w0; wv < w1; ++wv) {
+        u32 bits = bmap[wv];
+        pref[wv] = (unsigned short)pos;
+        while (bits) {
+          const int bb = __ffs(bits) - 1;
+          bits &= bits - 1;
+          kS[pos] = (unsigned short)((wv << 5) + bb);
+          if (BF16)
+            fuS_h[pos] = 0;
+          else
+            fuS_f[pos] = 0.f;
+          gacc[pos] = 0.f;
+          ++pos;
+        }
       }
     }
+    __syncthreads();
+    auto rank_of = [&](int k) -> int {
+      const int wv = k >> 5;
+      return (int)pref[wv] + __popc(bmap[wv] & ((1u << (k & 31)) - 1u));
+    };
+    // own row values into their slots (from the node's own support list)
+    for (int j = lane; j < su; j += WAVE) {
+      const int p_ = rank_of(sidx[offu + j]);
+      if (BF16)
+        fuS_h[p_] = pack1_bf16_rne(sval[offu + j]);
+      else
+        fuS_f[p_] = sval[offu + j];
+    }
+    {  // staged column ids -> slot positions, in place
+      for (int i = lane; i < total; i += WAVE)
+        nidx[i] = (unsigned short)rank_of((int)nidx[i]);
+    }
+    __syncthreads();
   }
-  __syncthreads();
-  auto rank_of = [&](int k) -> int {
-    const int wv = k >> 5;
-    return (int)pref[wv] + __popc(bmap[wv] & ((1u << (k & 31)) - 1u));
-  };
-  // own row values into their slots (from the node's own support list)
-  for (int j = lane; j < su; j += WAVE) {
-    const int p_ = rank_of(sidx[offu + j]);
-    if (BF16)
-      fuS_h[p_] = pack1_bf16_rne(sval[offu + j]);
-    else
-      fuS_f[p_] = sval[offu + j];
-  }
-  {  // staged column ids -> slot positions, in place
-    for (int i = lane; i < total; i += WAVE)
-      nidx[i] = (unsigned short)rank_of((int)nidx[i]);
-  }
-  __syncthreads();
 
   // phase 2: dots on 16-lane groups (4 edges at a time), then the
   // w-weighted scatter edge by edge in CSR order (plain read-add-write:
   // one edge's columns are distinct, the wave's LDS ops stay in order)
   double llh_acc = 0.0;
-  for (int et = 0; et < deg; et += 4) {
+  // SKIP: the node's edge sum of class grp — what group leader grp
+  // accumulates without SKIP, and what lane (grp, candidate) accumulates
+  // in phase 4 when every edge is empty
+  double cls = 0.0;
+  if (SKIP && quick) {
+    for (int i = grp; i < deg; i += 4) cls += c0;
+  } else if (SKIP) {
+    // Per chunk of 64 edges: the dots of the non-empty edges, four set
+    // bits at a time on the 16-lane groups (the same 16-lane stride and
+    // xor tree per edge, so the same x); lane e keeps x_e, 0.f for an
+    // empty edge.  Then p, w and the llh term once, lane-parallel over
+    // the edges (c0 falls out for an empty one); the terms add up per
+    // class e mod 4 in ascending e, as the group leaders do without SKIP
+    // (every lane with lane mod 4 == q carries class q); then the scatter
+    // over the set bits, ascending.
+    double acc = 0.0;
+    for (int c = 0; c < deg; c += WAVE) {
+      const u32 bs_l = chunk_bs(c);
+      const unsigned long long mask = __ballot((bs_l & 0xffffu) != 0u);
+      float x = 0.f;
+      for (unsigned long long m = mask; m;) {
+        int idx[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          idx[r] = m ? __ffsll(m) - 1 : -1;
+          m &= m - 1;  // 0 stays 0
+        }
+        const int mine = grp == 0   ? idx[0]
+                         : grp == 1 ? idx[1]
+                         : grp == 2 ? idx[2]
+                                    : idx[3];
+        const u32 bs = __shfl(bs_l, mine < 0 ? 0 : mine, WAVE);
+        const int base = (int)(bs >> 16);
+        const int sv = mine < 0 ? 0 : (int)(bs & 0xffffu);
+        float part = 0.f;
+        for (int j = gl; j < sv; j += 16) {
+          const int p_ = (int)nidx[base + j];
+          const float fv =
+              BF16 ? vget<true>(nval_h[base + j]) : nval_f[base + j];
+          const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
+          part += fu * fv;
+        }
+#pragma unroll
+        for (int off = 8; off > 0; off >>= 1)
+          part += __shfl_xor(part, off, WAVE);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float xr = __shfl(part, r << 4, WAVE);
+          if (lane == idx[r]) x = xr;
+        }
+      }
+      const float p = clamp_p(__expf(-x), min_p, max_p);
+      const float w = 1.f / (1.f - p);
+      const double term = (double)log1pf(-p) + (double)x;
+      const int nch = min(WAVE, deg - c);
+      for (int t = 0; t < nch; t += 4) {
+        const int src = t + (lane & 3);
+        const double v = __shfl(term, src, WAVE);
+        if (src < nch) acc += v;
+      }
+      for (unsigned long long m = mask; m; m &= m - 1) {
+        const int e = __ffsll(m) - 1;
+        const u32 bs = __shfl(bs_l, e, WAVE);
+        const float wq = __shfl(w, e, WAVE);
+        const int bq = (int)(bs >> 16);
+        const int sq = (int)(bs & 0xffffu);
+        for (int j = lane; j < sq; j += WAVE) {
+          const int p_ = (int)nidx[bq + j];
+          const float fv = BF16 ? vget<true>(nval_h[bq + j]) : nval_f[bq + j];
+          gacc[p_] += wq * fv;
+        }
+      }
+    }
+    cls = __shfl(acc, grp, WAVE);  // lane q < 4 carries class q
+  }
+  if (SKIP && gl == 0) llh_acc = cls;
+  for (int et = 0; et < deg && !SKIP; et += 4) {
     const int ei = et + grp;
     int base = 0, sv = 0;
     if (ei < deg) {
@@ -3375,23 +3511,42 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
   const bool live = gl < n_ladder;
   const float sj = live ? ladder[gl] : 0.f;
   double myllh = 0.0;
-  for (int et = 0; et < deg; et += 4) {
-    const int ei = et + grp;
-    if (ei < deg && live) {
-      const u32 bs = edge_bs(ei);
-      const int base = (int)(bs >> 16);
-      const int sv = (int)(bs & 0xffffu);
-      float x = 0.f;
-      for (int t = 0; t < sv; ++t) {
-        const int p_ = (int)nidx[base + t];
-        const float fv = BF16 ? vget<true>(nval_h[base + t]) : nval_f[base + t];
-        const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
-        const float c =
-            __builtin_amdgcn_fmed3f(fmaf(sj, gacc[p_], fu), min_f, max_f);
-        x = fmaf(c, fv, x);
+  auto trial_edge = [&](u32 bs) {
+    const int base = (int)(bs >> 16);
+    const int sv = (int)(bs & 0xffffu);
+    float x = 0.f;
+    for (int t = 0; t < sv; ++t) {
+      const int p_ = (int)nidx[base + t];
+      const float fv = BF16 ? vget<true>(nval_h[base + t]) : nval_f[base + t];
+      const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
+      const float c =
+          __builtin_amdgcn_fmed3f(fmaf(sj, gacc[p_], fu), min_f, max_f);
+      x = fmaf(c, fv, x);
+    }
+    const float p = clamp_p(__expf(-x), min_p, max_p);
+    myllh += (double)log1pf(-p) + (double)x;
+  };
+  if (SKIP && quick) {
+    if (live) myllh = cls;  // 0.0 + c0 + c0 ..., the chain of phase 4
+  } else if (SKIP) {
+    for (int c = 0; c < deg; c += WAVE) {
+      const u32 bs_l = chunk_bs(c);
+      const int nch = min(WAVE, deg - c);
+      for (int t = 0; t < nch; t += 4) {
+        const int src = t + grp;
+        const u32 bs = __shfl(bs_l, src, WAVE);
+        if (src < nch && live) {
+          if (bs & 0xffffu)
+            trial_edge(bs);
+          else
+            myllh += c0;
+        }
       }
-      const float p = clamp_p(__expf(-x), min_p, max_p);
-      myllh += (double)log1pf(-p) + (double)x;
+    }
+  } else {
+    for (int et = 0; et < deg; et += 4) {
+      const int ei = et + grp;
+      if (ei < deg && live) trial_edge(edge_bs(ei));
     }
   }
   float mynt = 0.f;
@@ -3459,7 +3614,7 @@ __host__ __device__ __forceinline__ int kfp_node_bytes(bool bf16, int nwp,
   return (q4 * (bf16 ? 16 : 20) + KFP_DEG * 4 + nwp * 2 + 15) & ~15;
 }
 
-template <bool BF16>
+template <bool BF16, bool SKIP>
 __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
     int K, const long long* __restrict__ indptr,
     const int* __restrict__ indices, const float* __restrict__ sumF,
@@ -3515,95 +3670,119 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
   // and the neighbour's list offset; 0 past the degree (an empty edge)
   u32 bs_l = 0u;
   long long off_l = 0;
-  if (gl < deg) {
+  // SKIP: with nothing staged every edge of the node is empty and its
+  // base is never used — the entry stays 0 without the dependent loads
+  if (gl < deg && !(SKIP && total == 0)) {
     bs_l = ((u32)epre[e0 + gl] << 16) |
            (u32)epre_len(epre, e0 + gl, gl, deg, total);
     off_l = soffset[indices[e0 + gl]];
   }
-  ebs[gl] = bs_l;  // the trial phase indexes edges per lane
-  {
-    uint4* bm4 = reinterpret_cast<uint4*>(smem);  // 4 bitmaps = nwp uint4
-    for (int i = lane; i < nwp; i += WAVE) bm4[i] = make_uint4(0, 0, 0, 0);
-  }
+  // SKIP: the group's non-empty edges (bit e = edge e), the quad's union
+  // (wave-uniform: it drives the edge loops), and the quad-uniform
+  // shortcut: no live group of the quad stages anything or has own
+  // support, so every active set is empty — no bitmap clear, no bitmap
+  // pass, no rank loop
+  const unsigned long long eb = __ballot((bs_l & 0xffffu) != 0u);
+  const u32 gm = (u32)(eb >> (grp * 16)) & 0xffffu;
+  const u32 um = (u32)(eb | (eb >> 16) | (eb >> 32) | (eb >> 48)) & 0xffffu;
+  const bool quick = SKIP && __ballot(total != 0 || su != 0) == 0ull;
+  const double c0 = empty_edge_term(min_p, max_p);
   int mdeg = max(deg, __shfl_xor(deg, 16, WAVE));
   mdeg = max(mdeg, __shfl_xor(mdeg, 32, WAVE));  // the quad's largest
-  __syncthreads();
+  // the loops that hold a cross-lane step: every edge up to the quad's
+  // largest degree, or (SKIP) the union's set bits, ascending
+  auto for_edges = [&](auto&& body_) {
+    if (SKIP) {
+      for (u32 m = um; m; m &= m - 1) body_(__ffs(m) - 1);
+    } else {
+      for (int e = 0; e < mdeg; ++e) body_(e);
+    }
+  };
+  int ns = 0;
+  if (!quick) {
+    ebs[gl] = bs_l;  // the trial phase indexes edges per lane
+    {
+      uint4* bm4 = reinterpret_cast<uint4*>(smem);  // 4 bitmaps = nwp uint4
+      for (int i = lane; i < nwp; i += WAVE) bm4[i] = make_uint4(0, 0, 0, 0);
+    }
+    __syncthreads();
 
-  // phase 1: stage the neighbour lists edge by edge, OR support bits
-  for (int e = 0; e < mdeg; ++e) {
-    const u32 bs = __shfl(bs_l, e, 16);
-    const long long off = __shfl(off_l, e, 16);
-    const int base = (int)(bs >> 16);
-    const int sv = (int)(bs & 0xffffu);
-    for (int j = gl; j < sv; j += 16) {
-      const int k = sidx[off + j];
-      nidx[base + j] = (unsigned short)k;
-      if (BF16)
-        nval_h[base + j] = pack1_bf16_rne(sval[off + j]);
-      else
-        nval_f[base + j] = sval[off + j];
+    // phase 1: stage the neighbour lists edge by edge, OR support bits
+    for_edges([&](int e) {
+      const u32 bs = __shfl(bs_l, e, 16);
+      const long long off = __shfl(off_l, e, 16);
+      const int base = (int)(bs >> 16);
+      const int sv = (int)(bs & 0xffffu);
+      for (int j = gl; j < sv; j += 16) {
+        const int k = sidx[off + j];
+        nidx[base + j] = (unsigned short)k;
+        if (BF16)
+          nval_h[base + j] = pack1_bf16_rne(sval[off + j]);
+        else
+          nval_f[base + j] = sval[off + j];
+        atomicOr(&bmap[k >> 5], 1u << (k & 31));
+      }
+    });
+    for (int j = gl; j < su; j += 16) {
+      const int k = sidx[offu + j];
       atomicOr(&bmap[k >> 5], 1u << (k & 31));
     }
-  }
-  for (int j = gl; j < su; j += 16) {
-    const int k = sidx[offu + j];
-    atomicOr(&bmap[k >> 5], 1u << (k & 31));
-  }
-  __syncthreads();
+    __syncthreads();
 
-  // phase 1.5: bitmap scan over the group's 16 lanes -> sorted compact
-  // kS, per-word exclusive prefix, zeroed gacc/fuS slots
-  const int wchunk = (nw + 15) >> 4;
-  const int w0 = min(gl * wchunk, nw);
-  const int w1 = min(w0 + wchunk, nw);
-  int cnt = 0;
-  for (int wv = w0; wv < w1; ++wv) cnt += __popc(bmap[wv]);
-  int incl = cnt;
+    // phase 1.5: bitmap scan over the group's 16 lanes -> sorted compact
+    // kS, per-word exclusive prefix, zeroed gacc/fuS slots
+    const int wchunk = (nw + 15) >> 4;
+    const int w0 = min(gl * wchunk, nw);
+    const int w1 = min(w0 + wchunk, nw);
+    int cnt = 0;
+    for (int wv = w0; wv < w1; ++wv) cnt += __popc(bmap[wv]);
+    int incl = cnt;
 #pragma unroll
-  for (int off = 1; off < 16; off <<= 1) {
-    const int v = __shfl_up(incl, off, 16);
-    if (gl >= off) incl += v;
-  }
-  const int ns = __shfl(incl, 15, 16);
-  if (cnt) {
-    int p_ = incl - cnt;
-    for (int wv = w0; wv < w1; ++wv) {
-      u32 bits = bmap[wv];
-      pref[wv] = (unsigned short)p_;
-      while (bits) {
-        const int bb = __ffs(bits) - 1;
-        bits &= bits - 1;
-        kS[p_] = (unsigned short)((wv << 5) + bb);
-        if (BF16)
-          fuS_h[p_] = 0;
-        else
-          fuS_f[p_] = 0.f;
-        gacc[p_] = 0.f;
-        ++p_;
+    for (int off = 1; off < 16; off <<= 1) {
+      const int v = __shfl_up(incl, off, 16);
+      if (gl >= off) incl += v;
+    }
+    ns = __shfl(incl, 15, 16);
+    if (cnt) {
+      int p_ = incl - cnt;
+      for (int wv = w0; wv < w1; ++wv) {
+        u32 bits = bmap[wv];
+        pref[wv] = (unsigned short)p_;
+        while (bits) {
+          const int bb = __ffs(bits) - 1;
+          bits &= bits - 1;
+          kS[p_] = (unsigned short)((wv << 5) + bb);
+          if (BF16)
+            fuS_h[p_] = 0;
+          else
+            fuS_f[p_] = 0.f;
+          gacc[p_] = 0.f;
+          ++p_;
+        }
       }
     }
+    __syncthreads();
+    auto rank_of = [&](int k) -> int {
+      const int wv = k >> 5;
+      return (int)pref[wv] + __popc(bmap[wv] & ((1u << (k & 31)) - 1u));
+    };
+    for (int j = gl; j < su; j += 16) {
+      const int p_ = rank_of(sidx[offu + j]);
+      if (BF16)
+        fuS_h[p_] = pack1_bf16_rne(sval[offu + j]);
+      else
+        fuS_f[p_] = sval[offu + j];
+    }
+    for (int i = gl; i < total; i += 16)
+      nidx[i] = (unsigned short)rank_of((int)nidx[i]);
+    __syncthreads();
   }
-  __syncthreads();
-  auto rank_of = [&](int k) -> int {
-    const int wv = k >> 5;
-    return (int)pref[wv] + __popc(bmap[wv] & ((1u << (k & 31)) - 1u));
-  };
-  for (int j = gl; j < su; j += 16) {
-    const int p_ = rank_of(sidx[offu + j]);
-    if (BF16)
-      fuS_h[p_] = pack1_bf16_rne(sval[offu + j]);
-    else
-      fuS_f[p_] = sval[offu + j];
-  }
-  for (int i = gl; i < total; i += 16)
-    nidx[i] = (unsigned short)rank_of((int)nidx[i]);
-  __syncthreads();
 
   // phase 2: the dots of all edges first (lane e keeps x_e), the
   // transcendentals once over the edge lanes, then the scatter edge by
   // edge in CSR order with w_e broadcast
   float x = 0.f;
-  for (int e = 0; e < mdeg; ++e) {
+  for_edges([&](int e) {
     const u32 bs = __shfl(bs_l, e, 16);
     const int base = (int)(bs >> 16);
     const int sv = (int)(bs & 0xffffu);
@@ -3617,7 +3796,7 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
 #pragma unroll
     for (int off = 8; off > 0; off >>= 1) part += __shfl_xor(part, off, WAVE);
     if (gl == e) x = part;
-  }
+  });
   const float p = clamp_p(__expf(-x), min_p, max_p);
   const float w = 1.f / (1.f - p);
   double llh_acc;
@@ -3630,7 +3809,7 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
     const double a = t + __shfl_down(t, 2, 16);  // A0 + A2 | A1 + A3
     llh_acc = __shfl(a + __shfl_down(a, 1, 16), 0, 16);
   }
-  for (int e = 0; e < mdeg; ++e) {
+  for_edges([&](int e) {
     const u32 bs = __shfl(bs_l, e, 16);
     const float wq = __shfl(w, e, 16);
     const int bq = (int)(bs >> 16);
@@ -3640,7 +3819,7 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
       const float fv = BF16 ? vget<true>(nval_h[bq + j]) : nval_f[bq + j];
       gacc[p_] += wq * fv;
     }
-  }
+  });
   __syncthreads();
 
   // phase 3: finalize g in place + write the global pools; the node sums
@@ -3695,7 +3874,9 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
     for (int et = 0; et < deg; et += 4) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        if (et + q < deg) {
+        if (SKIP && et + q < deg && !((gm >> (et + q)) & 1u)) {
+          m[q] += c0;  // empty edge: the term at x = 0.f, same chain
+        } else if (et + q < deg) {
           const u32 bs = ebs[et + q];
           const int base = (int)(bs >> 16);
           const int sv = (int)(bs & 0xffffu);
@@ -3813,8 +3994,14 @@ __global__ void __launch_bounds__(BLOCK) k3s_commit_t(
 }
 
 // K3W: the same commit and list rewrite for the WAVE class, one wave per
-// node (four nodes per 256-thread block).  The routed order is laid out
-// [block | wave], so wave w serves pack position blk0 + w, as KFW does.
+// K3W_G consecutive positions.  The routed order is laid out
+// [block | wave], so wave w serves pack positions blk0 + w * K3W_G ...
+// Most positions have nothing to commit (a rejected step, or an empty
+// active set): lanes load order / best / gcount and the pool offsets of
+// their positions lane-parallel, clear the dirty flags lane-parallel, and
+// a ballot picks the positions with s > 0 and ns > 0; only those run the
+// rounds below, one after the other, with the node's scalars broadcast
+// from the owning lane.  A rejected position costs a lane, not a wave.
 // Invariant: a wave-class node has ns = gcount <= bound <= wcap <= cap
 // (routing + KFW; the binding checks wcap <= cap), so the rewritten list
 // (a subset of the ns active entries) always fits its cap-strided slot —
@@ -3825,6 +4012,16 @@ __global__ void __launch_bounds__(BLOCK) k3s_commit_t(
 // ascending, so the list stays ascending in k.  No LDS, no barrier, no
 // second read of F, no atomics: deterministic, and element-wise the same
 // arithmetic as K3S (bitwise-equal F, scount and lists).
+
+// Positions per wave of K3W.  Accepted nodes of one wave commit serially
+// (each a chain of dependent loads), so the grid must still fill the
+// machine when most nodes accept: 16 keeps > 8192 waves (32 per CU) down
+// to ~131k wave-class nodes.  Values tried: profiles/r09_skip_empty.md.
+#ifndef K3W_G
+#define K3W_G 16
+#endif
+static_assert(K3W_G >= 16 && K3W_G <= WAVE, "K3W_G must be in [16, 64]");
+
 template <bool BF16>
 __global__ void __launch_bounds__(BLOCK) k3w_commit_t(
     void* __restrict__ Fp, int ldF, const int* __restrict__ order, int blk0,
@@ -3835,44 +4032,65 @@ __global__ void __launch_bounds__(BLOCK) k3w_commit_t(
     float* __restrict__ sval, int* __restrict__ scount,
     unsigned char* __restrict__ dirty, float min_f, float max_f) {
   const int lane = threadIdx.x & (WAVE - 1);
-  const int w = blockIdx.x * NWAVE + (threadIdx.x >> 6);
-  if (w >= n_wave) return;  // tail waves of the last block (wave-uniform)
-  const int b = blk0 + w;
-  const int u = order[b];
-  if (dirty != nullptr && lane == 0) dirty[u] = 0;
-  const float s = best[u];
-  if (s <= 0.f) return;  // wave-uniform: F and the lists stay untouched
-  const int ns = gcount[b];
-  const long long go = goffset[b];
-  const long long so = soffset[u];
-  const unsigned long long below = (1ull << lane) - 1ull;
-  int running = 0;
-  for (int base = 0; base < ns; base += WAVE) {
-    const int i = base + lane;
-    int k = 0;
-    float nf = 0.f;
-    if (i < ns) {
-      k = gidx[go + i];
-      const float f = f_elem<BF16>(Fp, ldF, u, k);
-      nf = __builtin_amdgcn_fmed3f(fmaf(s, gval[go + i], f), min_f, max_f);
-      if (BF16) {
-        const unsigned short h = pack1_bf16_rne(nf);
-        reinterpret_cast<unsigned short*>(Fp)[(size_t)u * ldF + k] = h;
-        nf = __uint_as_float((u32)h << 16);  // post-round value
-      } else {
-        reinterpret_cast<float*>(Fp)[(size_t)u * ldF + k] = nf;
-      }
-    }
-    const bool keep = nf != 0.f;  // lanes past ns hold 0
-    const unsigned long long bal = __ballot(keep);
-    if (keep) {
-      const long long at = so + running + __popcll(bal & below);
-      sidx[at] = k;
-      sval[at] = nf;
-    }
-    running += __popcll(bal);
+  const int p0 = (blockIdx.x * NWAVE + (threadIdx.x >> 6)) * K3W_G;
+  if (p0 >= n_wave) return;  // tail waves of the last block (wave-uniform)
+  // lane l < K3W_G owns position p0 + l: its node, step, entry count and
+  // the two pool offsets are loaded lane-parallel, its dirty flag cleared
+  const bool have = lane < K3W_G && p0 + lane < n_wave;
+  int u_l = 0, ns_l = 0;
+  float s_l = 0.f;
+  long long go_l = 0, so_l = 0;
+  if (have) {
+    const int b = blk0 + p0 + lane;
+    u_l = order[b];
+    ns_l = gcount[b];
+    go_l = goffset[b];
+    s_l = best[u_l];
+    so_l = soffset[u_l];
+    if (dirty != nullptr) dirty[u_l] = 0;
   }
-  if (lane == 0) scount[u] = running;
+  // a rejected node (s <= 0) leaves F and the lists untouched; an accepted
+  // one with no entries has an empty list
+  const bool accept = have && !(s_l <= 0.f);
+  if (accept && ns_l == 0) scount[u_l] = 0;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  // the rounds run only for the positions with something to commit
+  for (unsigned long long todo = __ballot(accept && ns_l > 0); todo;
+       todo &= todo - 1) {
+    const int src = __ffsll(todo) - 1;
+    const int u = __shfl(u_l, src, WAVE);
+    const float s = __shfl(s_l, src, WAVE);
+    const int ns = __shfl(ns_l, src, WAVE);
+    const long long go = __shfl(go_l, src, WAVE);
+    const long long so = __shfl(so_l, src, WAVE);
+    int running = 0;
+    for (int base = 0; base < ns; base += WAVE) {
+      const int i = base + lane;
+      int k = 0;
+      float nf = 0.f;
+      if (i < ns) {
+        k = gidx[go + i];
+        const float f = f_elem<BF16>(Fp, ldF, u, k);
+        nf = __builtin_amdgcn_fmed3f(fmaf(s, gval[go + i], f), min_f, max_f);
+        if (BF16) {
+          const unsigned short h = pack1_bf16_rne(nf);
+          reinterpret_cast<unsigned short*>(Fp)[(size_t)u * ldF + k] = h;
+          nf = __uint_as_float((u32)h << 16);  // post-round value
+        } else {
+          reinterpret_cast<float*>(Fp)[(size_t)u * ldF + k] = nf;
+        }
+      }
+      const bool keep = nf != 0.f;  // lanes past ns hold 0
+      const unsigned long long bal = __ballot(keep);
+      if (keep) {
+        const long long at = so + running + __popcll(bal & below);
+        sidx[at] = k;
+        sval[at] = nf;
+      }
+      running += __popcll(bal);
+    }
+    if (lane == 0) scount[u] = running;
+  }
 }
 
 // ------------------------------------------------- list-based column sum
@@ -4586,27 +4804,28 @@ extern "C" void launch_kfw(int bf16, const long long* indptr,
                            const float* GGp, const float* ladder,
                            float* best, int n_ladder, int wcap, int K,
                            float alpha, float min_p, float max_p,
-                           float min_f, float max_f, hipStream_t stream) {
+                           float min_f, float max_f, int skip,
+                           hipStream_t stream) {
   if (n_blocks == 0) return;
   if (n_ladder > 16) throw std::runtime_error("ladder length > 16 unsupported");
   const size_t lds = (size_t)kfw_lds_bytes(bf16, K, wcap);
   if (lds > 160 * 1024)
     throw std::runtime_error("KFW: wcap exceeds the workgroup LDS budget");
+#define KFW_LAUNCH(BF, SK)                                                  \
+  do {                                                                      \
+    allow_large_lds((const void*)&kfw_sparse_t<BF, SK>, lds);               \
+    hipLaunchKernelGGL((kfw_sparse_t<BF, SK>), dim3(n_blocks), dim3(WAVE),  \
+                       lds, stream, K, indptr, indices, sumF, order, blk0,  \
+                       pos, soffset, sidx, sval, scount, epre, bound,       \
+                       goffset, gidx, gval, gcount, llh, GGp, ladder, best, \
+                       n_ladder, wcap, alpha, min_p, max_p, min_f, max_f);  \
+  } while (0)
   if (bf16) {
-    allow_large_lds((const void*)&kfw_sparse_t<true>, lds);
-    hipLaunchKernelGGL((kfw_sparse_t<true>), dim3(n_blocks), dim3(WAVE), lds,
-                       stream, K, indptr, indices, sumF, order, blk0, pos,
-                       soffset, sidx, sval, scount, epre, bound, goffset, gidx,
-                       gval, gcount, llh, GGp, ladder, best, n_ladder, wcap,
-                       alpha, min_p, max_p, min_f, max_f);
+    if (skip) KFW_LAUNCH(true, true); else KFW_LAUNCH(true, false);
   } else {
-    allow_large_lds((const void*)&kfw_sparse_t<false>, lds);
-    hipLaunchKernelGGL((kfw_sparse_t<false>), dim3(n_blocks), dim3(WAVE), lds,
-                       stream, K, indptr, indices, sumF, order, blk0, pos,
-                       soffset, sidx, sval, scount, epre, bound, goffset, gidx,
-                       gval, gcount, llh, GGp, ladder, best, n_ladder, wcap,
-                       alpha, min_p, max_p, min_f, max_f);
+    if (skip) KFW_LAUNCH(false, true); else KFW_LAUNCH(false, false);
   }
+#undef KFW_LAUNCH
   HIP_CHECK(hipGetLastError());
 }
 
@@ -4633,32 +4852,35 @@ extern "C" void launch_kfp(int bf16, const long long* indptr,
                            const float* GGp, const float* ladder,
                            float* best, int n_ladder, int qcap, int K,
                            float alpha, float min_p, float max_p,
-                           float min_f, float max_f, hipStream_t stream) {
+                           float min_f, float max_f, int skip,
+                           hipStream_t stream) {
   if (n_pack == 0) return;
   if (n_ladder > 16) throw std::runtime_error("ladder length > 16 unsupported");
   const size_t lds = (size_t)kfp_lds_bytes(bf16, K, qcap);
   if (qcap <= 0 || qcap > 65535 || lds > 64 * 1024)
     throw std::runtime_error("KFP: qcap exceeds the workgroup LDS budget");
   const int grid = (n_pack + KFP_NODES - 1) / KFP_NODES;
+#define KFP_LAUNCH(BF, SK)                                                  \
+  hipLaunchKernelGGL((kfp_sparse_t<BF, SK>), dim3(grid), dim3(WAVE), lds,   \
+                     stream, K, indptr, indices, sumF, order, pos, n_pack,  \
+                     soffset, sidx, sval, scount, epre, bound, goffset,     \
+                     gidx, gval, gcount, llh, GGp, ladder, best, n_ladder,  \
+                     qcap, alpha, min_p, max_p, min_f, max_f)
   if (bf16) {
-    hipLaunchKernelGGL((kfp_sparse_t<true>), dim3(grid), dim3(WAVE), lds,
-                       stream, K, indptr, indices, sumF, order, pos, n_pack,
-                       soffset, sidx, sval, scount, epre, bound, goffset, gidx,
-                       gval, gcount, llh, GGp, ladder, best, n_ladder, qcap,
-                       alpha, min_p, max_p, min_f, max_f);
+    if (skip) KFP_LAUNCH(true, true); else KFP_LAUNCH(true, false);
   } else {
-    hipLaunchKernelGGL((kfp_sparse_t<false>), dim3(grid), dim3(WAVE), lds,
-                       stream, K, indptr, indices, sumF, order, pos, n_pack,
-                       soffset, sidx, sval, scount, epre, bound, goffset, gidx,
-                       gval, gcount, llh, GGp, ladder, best, n_ladder, qcap,
-                       alpha, min_p, max_p, min_f, max_f);
+    if (skip) KFP_LAUNCH(false, true); else KFP_LAUNCH(false, false);
   }
+#undef KFP_LAUNCH
   HIP_CHECK(hipGetLastError());
 }
 
+extern "C" int k3w_group() { return K3W_G; }
+
 // Sparse commit of a routed order laid out [block | wave]: positions
 // [0, n_block) one block per node (K3S), [n_block, n_total) one wave per
-// node, four per workgroup (K3W).  dirty may be null (flags not kept).
+// K3W_G positions, four waves per workgroup (K3W).  dirty may be null
+// (flags not kept).
 extern "C" void launch_k3s(void* F, int bf16, const int* order, int n_block,
                            int n_total, const long long* goffset,
                            const int* gidx, const float* gval,
@@ -4667,7 +4889,7 @@ extern "C" void launch_k3s(void* F, int bf16, const int* order, int n_block,
                            int* scount, unsigned char* dirty, int cap, int K,
                            float min_f, float max_f, hipStream_t stream) {
   const int n_wave = n_total - n_block;
-  const int wgrid = (n_wave + NWAVE - 1) / NWAVE;
+  const int wgrid = (n_wave + NWAVE * K3W_G - 1) / (NWAVE * K3W_G);
   if (bf16) {
     if (n_block > 0)
       hipLaunchKernelGGL((k3s_commit_t<true>), dim3(n_block), dim3(BLOCK), 0,

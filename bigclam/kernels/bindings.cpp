@@ -402,8 +402,9 @@ extern "C" void launch_kfw(int, const long long*, const int*, const float*,
                            const int*, const int*, const long long*, int*,
                            float*, int*, double*, const float*, const float*,
                            float*, int, int, int, float, float, float,
-                           float, float, hipStream_t);
+                           float, float, int, hipStream_t);
 extern "C" long long kfw_lds_bytes(int, int, int);
+extern "C" int k3w_group();
 extern "C" long long kfp_lds_bytes(int, int, int);
 extern "C" void launch_kfp(int, const long long*, const int*, const float*,
                            const int*, const int*, int, const long long*,
@@ -411,7 +412,7 @@ extern "C" void launch_kfp(int, const long long*, const int*, const float*,
                            const int*, const int*, const long long*, int*,
                            float*, int*, double*, const float*, const float*,
                            float*, int, int, int, float, float, float,
-                           float, float, hipStream_t);
+                           float, float, int, hipStream_t);
 extern "C" void launch_k3s(void*, int, const int*, int, int,
                            const long long*, const int*, const float*,
                            const int*, const float*, const long long*, int*,
@@ -496,13 +497,16 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
                   torch::Tensor best, int64_t cap, double alpha,
                   double min_p, double max_p, double min_f, double max_f,
                   int64_t n_block, int64_t wcap, int64_t qcap,
-                  std::optional<torch::Tensor> wsplit, int64_t n_pack) {
+                  std::optional<torch::Tensor> wsplit, int64_t n_pack,
+                  bool skip) {
   // order[:n_block] runs the block kernel (KFS), order[n_block:] the
   // one-wave-per-node kernel (KFW, bound <= wcap); pools and gcount are
   // indexed by position in `order` for both.  With qcap > 0 and the
   // routing's wsplit, the wave class runs as two launches: the pack
   // positions wsplit[:n_pack] four nodes per wave (KFP), the rest
-  // wsplit[n_pack:n_wave] one wave per node (KFW).
+  // wsplit[n_pack:n_wave] one wave per node (KFW).  skip selects the
+  // KFW/KFP instantiations that pass over empty edges and empty active
+  // sets (bitwise the same outputs; false = the A/B reference).
   CHECK_F(F);
   CHECK_IN(indptr, torch::kInt64);
   CHECK_IN(indices, torch::kInt32);
@@ -571,7 +575,7 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
                GG.data_ptr<float>(), ladder.data_ptr<float>(),
                best.data_ptr<float>(), (int)ladder.size(0), (int)wcap,
                (int)F.size(1), (float)alpha, (float)min_p, (float)max_p,
-               (float)min_f, (float)max_f, wave_s);
+               (float)min_f, (float)max_f, skip ? 1 : 0, wave_s);
   if (side) TORCH_CHECK(hipEventRecord(side->join, wave_s) == hipSuccess);
   if (packed)
     launch_kfp(is_bf16(F) ? 1 : 0, i64p(indptr), indices.data_ptr<int>(),
@@ -584,7 +588,7 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
                GG.data_ptr<float>(), ladder.data_ptr<float>(),
                best.data_ptr<float>(), (int)ladder.size(0), (int)qcap,
                (int)F.size(1), (float)alpha, (float)min_p, (float)max_p,
-               (float)min_f, (float)max_f, main_s);
+               (float)min_f, (float)max_f, skip ? 1 : 0, main_s);
   if (side)
     TORCH_CHECK(hipStreamWaitEvent(main_s, side->join, 0) == hipSuccess);
   launch_kfs(F.data_ptr(), is_bf16(F) ? 1 : 0,
@@ -995,7 +999,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("min_p"), py::arg("max_p"), py::arg("min_f"),
         py::arg("max_f"), py::arg("n_block"), py::arg("wcap"),
         py::arg("qcap") = 0, py::arg("wsplit") = py::none(),
-        py::arg("n_pack") = 0);
+        py::arg("n_pack") = 0, py::arg("skip") = true);
+  m.def("sparse_commit_group", []() { return (int64_t)k3w_group(); },
+        "wave-class positions one wave of the sparse commit (K3W) serves");
   m.def("sparse_pack_lds_bytes",
         [](bool bf16, int64_t K, int64_t qcap) {
           return (int64_t)kfp_lds_bytes(bf16 ? 1 : 0, (int)K, (int)qcap);

@@ -284,6 +284,7 @@ def sparse_sweep_part(
     qcap: int = 0,
     wsplit: torch.Tensor = None,
     n_pack: int = 0,
+    skip: bool = True,
 ):
     """KFS/KFW for the routed (sparse) nodes: the compact gradient pools,
     llh per node, and the Armijo best step.  ``order_sparse[:n_block]``
@@ -297,7 +298,9 @@ def sparse_sweep_part(
     (computed here when not given).  With ``qcap > 0`` and the routing's
     ``wsplit``, the wave class runs as two launches: the pack positions
     ``wsplit[:n_pack]`` four nodes per wave (KFP), the rest one wave per
-    node; the outputs are bitwise the same either way."""
+    node; the outputs are bitwise the same either way.  ``skip`` selects
+    the KFW/KFP builds that pass over empty edges and empty active sets
+    (``ShardState.sparse_skip``); again bitwise the same outputs."""
     ext = ensure_loaded()
     dev = F.device
     n_s = int(order_sparse.numel())
@@ -314,7 +317,7 @@ def sparse_sweep_part(
         F, indptr, indices, sumF, order_sparse, soffset, sidx, sval, scount,
         epre, bound, goffset, gidx, gval, gcount, llh_out, GG, _ladder(cfg, dev),
         best_out, cap, cfg.alpha, cfg.min_p, cfg.max_p, cfg.min_f, cfg.max_f,
-        int(n_block), int(wcap), int(qcap), wsplit, int(n_pack),
+        int(n_block), int(wcap), int(qcap), wsplit, int(n_pack), bool(skip),
     )
     return {
         "order": order_sparse,
