@@ -819,7 +819,7 @@ class ShardState:
         pack = ops.sparse_sweep_part(
             self.F, self.indptr, self.indices, self.sumF, order_s,
             soffset, sidx, sval, scount, epre, bound32, goffset,
-            self.n_local * cap, cap, llh, best, self.cfg,
+            cap, llh, best, self.cfg,
             state_pools=(self._sp_gidx, self._sp_gval),
             n_block=n_blk, wcap=wcap, GG=GG,
             qcap=qcap if wsplit is not None else 0, wsplit=wsplit,

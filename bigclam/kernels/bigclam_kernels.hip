@@ -49,6 +49,9 @@
 //   -Fu'.(sumF - Fu + Fu') + Fu'.Fu' == Fu'.(Fu - sumF).
 
 #include <hip/hip_runtime.h>
+#include <type_traits>
+
+#include "sparse_sweep.h"
 
 #define WAVE 64
 #define BLOCK 256
@@ -2567,7 +2570,6 @@ __global__ void __launch_bounds__(BLOCK) kaf_support_t(
 #define RT_GRP 16      // lanes per node in the bounds walk
 #define RT_HUB 512     // degree above which the whole block walks the node
 #define RT_SCAN 1024   // threads of the single scan block
-#define KFP_DEG 16     // most edges of a node on the packed wave path (KFP)
 
 __device__ __forceinline__ int sat_add(int a, int b, int sat) {
   return min(a + b, sat);
@@ -2838,6 +2840,228 @@ __device__ __forceinline__ int epre_len(const int* __restrict__ epre,
   return (i + 1 < deg ? epre[e + 1] : total) - epre[e];
 }
 
+// ---- shared by KFS, KFW and KFP (docs/kernels.md, "Shared sweep code") ----
+// SweepView: a kernel's dynamic LDS through its layout (sparse_sweep.h);
+// the bf16 | fp32 storage of staged values and own row lives in its
+// accessors only.  The helpers are the loop bodies the kernels share; G is
+// the lane stride, `l` the lane's index within its G lanes.  KFP == KFW and
+// SKIP == non-SKIP bitwise because all run these same expressions in order.
+#define SWEEP_FN __device__ __forceinline__
+
+template <bool BF16>
+struct SweepView {
+  using val_t = std::conditional_t<BF16, unsigned short, float>;
+  u32 *bmap, *ebs;
+  float *gacc, *sfS;  // sfS: KFS keeps the finalized gradient (gS) here
+  unsigned short *nidx, *kS, *pref;
+  val_t *nv, *fv;
+
+  SWEEP_FN SweepView(char* m, const SweepLds& L)
+      : bmap((u32*)(m + L.bmap)), ebs((u32*)(m + L.ebs)),
+        gacc((float*)(m + L.gacc)), sfS((float*)(m + L.sf)),
+        nidx((unsigned short*)(m + L.nidx)), kS((unsigned short*)(m + L.kS)),
+        pref((unsigned short*)(m + L.pref)), nv((val_t*)(m + L.nval)),
+        fv((val_t*)(m + L.fu)) {}
+
+  static SWEEP_FN float up(val_t v) {
+    if constexpr (BF16) return __uint_as_float((u32)v << 16);
+    else return v;
+  }
+  static SWEEP_FN val_t down(float v) {
+    if constexpr (BF16) return pack1_bf16_rne(v);
+    else return v;
+  }
+  SWEEP_FN float nval(int i) const { return up(nv[i]); }
+  SWEEP_FN float fu(int i) const { return up(fv[i]); }
+  SWEEP_FN void set_nval(int i, float v) const { nv[i] = down(v); }
+  SWEEP_FN void set_fu(int i, float v) const { fv[i] = down(v); }
+  SWEEP_FN void zero_slot(int i) const { fv[i] = 0, gacc[i] = 0.f; }
+  // slot of an active column: its word's exclusive prefix + the popcount
+  // of the word's lower bits
+  SWEEP_FN int rank_of(int k) const {
+    const int wv = k >> 5;
+    return (int)pref[wv] + __popc(bmap[wv] & ((1u << (k & 31)) - 1u));
+  }
+};
+
+// stage one neighbour list at `base` and OR its columns into the bitmap
+template <int G, class V>
+SWEEP_FN void stage_list(const V& s, const int* sidx, const float* sval,
+                         long long off, int base, int sv, int l) {
+  for (int j = l; j < sv; j += G) {
+    const int k = sidx[off + j];
+    s.nidx[base + j] = (unsigned short)k;
+    s.set_nval(base + j, sval[off + j]);
+    atomicOr(&s.bmap[k >> 5], 1u << (k & 31));
+  }
+}
+
+// OR the node's own support into the bitmap
+template <int G, class V>
+SWEEP_FN void or_own_bits(const V& s, const int* sidx, long long offu, int su,
+                          int l) {
+  for (int j = l; j < su; j += G) {
+    const int k = sidx[offu + j];
+    atomicOr(&s.bmap[k >> 5], 1u << (k & 31));
+  }
+}
+
+// bitmap words [w0, w1) -> sorted kS from `pos`, pref, init(slot, column)
+template <class V, class Init>
+SWEEP_FN void emit_words(const V& s, int w0, int w1, int pos, Init&& init) {
+  for (int wv = w0; wv < w1; ++wv) {
+    u32 bits = s.bmap[wv];
+    s.pref[wv] = (unsigned short)pos;
+    while (bits) {
+      const int b = __ffs(bits) - 1;
+      bits &= bits - 1;
+      const int k = (wv << 5) + b;
+      s.kS[pos] = (unsigned short)k;
+      init(pos, k);
+      ++pos;
+    }
+  }
+}
+
+// KFW / KFP bitmap scan over G lanes: count the lane's word range, place
+// it by an inclusive __shfl_up scan, emit with zeroed slots (nothing for
+// an empty range: pref is only read through a set bit).  Returns |S_u|.
+template <int G, class V>
+SWEEP_FN int bitmap_scan(const V& s, int nw, int l) {
+  const int wchunk = (nw + G - 1) / G;
+  const int w0 = min(l * wchunk, nw);
+  const int w1 = min(w0 + wchunk, nw);
+  int cnt = 0;
+  for (int wv = w0; wv < w1; ++wv) cnt += __popc(s.bmap[wv]);
+  int incl = cnt;
+#pragma unroll
+  for (int off = 1; off < G; off <<= 1) {
+    const int v = __shfl_up(incl, off, G);
+    if (l >= off) incl += v;
+  }
+  const int ns = __shfl(incl, G - 1, G);
+  if (cnt)
+    emit_words(s, w0, w1, incl - cnt, [&](int p_, int) { s.zero_slot(p_); });
+  return ns;
+}
+
+// staged column ids -> slot positions, in place (each is in the bitmap)
+template <int G, class V>
+SWEEP_FN void to_slots(const V& s, int total, int l) {
+  for (int i = l; i < total; i += G)
+    s.nidx[i] = (unsigned short)s.rank_of((int)s.nidx[i]);
+}
+
+// own row values into their slots, from the node's own support list
+template <int G, class V>
+SWEEP_FN void own_values(const V& s, const int* sidx, const float* sval,
+                         long long offu, int su, int l) {
+  for (int j = l; j < su; j += G)
+    s.set_fu(s.rank_of(sidx[offu + j]), sval[offu + j]);
+}
+
+// this lane's part of fu . fv over one staged list
+template <int G, class V>
+SWEEP_FN float list_dot(const V& s, int base, int sv, int l) {
+  float part = 0.f;
+  for (int j = l; j < sv; j += G) {
+    const int p_ = (int)s.nidx[base + j];
+    const float fv = s.nval(base + j);
+    const float fu = s.fu(p_);
+    part += fu * fv;
+  }
+  return part;
+}
+
+// one edge's dot on a 16-lane group: stride 16, then the xor 8/4/2/1 fold
+template <class V>
+SWEEP_FN float group_dot(const V& s, int base, int sv, int gl) {
+  float part = list_dot<16>(s, base, sv, gl);
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) part += __shfl_xor(part, off, WAVE);
+  return part;
+}
+
+// gacc += w * fv over one list, plain read-add-write (distinct slots)
+template <int G, class V>
+SWEEP_FN void list_scatter(const V& s, int base, int sv, float w, int l) {
+  for (int j = l; j < sv; j += G) {
+    const int p_ = (int)s.nidx[base + j];
+    const float fv = s.nval(base + j);
+    s.gacc[p_] += w * fv;
+  }
+}
+
+// phase 3 at slot i: g = gacc - sumF + f to the pools + the node sums.
+// INPLACE (KFW / KFP): g -> gacc, sumF[k] -> sfS; else (KFS) g -> sfS.
+template <bool INPLACE, class V>
+SWEEP_FN void finalize_slot(const V& s, int i, const float* sumF, int* gidx,
+                            float* gval, long long go, float& gg, float& fs,
+                            float& ff) {
+  const int k = (int)s.kS[i];
+  const float f = s.fu(i);
+  const float sfk = sumF[k];
+  const float g = s.gacc[i] - sfk + f;
+  if (INPLACE) s.gacc[i] = g;
+  s.sfS[i] = INPLACE ? sfk : g;
+  gidx[go + i] = k;
+  gval[go + i] = g;
+  gg += g * g - sfk * sfk;
+  fs = fmaf(f, sfk, fs);
+  ff = fmaf(f, f, ff);
+}
+
+// p of an edge from its dot, and the edge's llh term
+SWEEP_FN float edge_p(float x, float min_p, float max_p) {
+  return clamp_p(__expf(-x), min_p, max_p);
+}
+SWEEP_FN double edge_term(float p, float x) {
+  return (double)log1pf(-p) + (double)x;
+}
+// The llh term and every trial term of an edge whose neighbour list is
+// empty (the dot is 0.f whatever the step): the same expression at
+// x = 0.f on the same inputs, bitwise what the edge loops would recompute.
+SWEEP_FN double empty_edge_term(float min_p, float max_p) {
+  return edge_term(edge_p(0.f, min_p, max_p), 0.f);
+}
+
+// one edge's llh term at trial step sj (g = finalized gradient by slot)
+template <class V>
+SWEEP_FN double trial_edge_term(const V& s, const float* g, int base, int sv,
+                                float sj, float min_p, float max_p,
+                                float min_f, float max_f) {
+  float x = 0.f;
+  for (int t = 0; t < sv; ++t) {
+    const int p_ = (int)s.nidx[base + t];
+    const float fv = s.nval(base + t);
+    const float fu = s.fu(p_);
+    const float c = __builtin_amdgcn_fmed3f(fmaf(sj, g[p_], fu), min_f, max_f);
+    x = fmaf(c, fv, x);
+  }
+  return edge_term(edge_p(x, min_p, max_p), x);
+}
+
+// the trial node term of slot i added to acc; sfk = sumF at the slot
+template <class V>
+SWEEP_FN float trial_node_term(const V& s, const float* g, int i, float sfk,
+                               float sj, float min_f, float max_f, float acc) {
+  const float fu = s.fu(i);
+  const float c = __builtin_amdgcn_fmed3f(fmaf(sj, g[i], fu), min_f, max_f);
+  return fmaf(c, fu - sfk, acc);
+}
+
+// Armijo pick over W candidate lanes starting at lane `shift` of the
+// wave: the first step that passes, 0.f if none does
+template <int W>
+SWEEP_FN float armijo_pick(bool live, double trial, float nt, double llh_base,
+                           float alpha, float sj, float gg, int shift) {
+  const bool ok =
+      live && (trial + (double)nt >= llh_base + (double)(alpha * sj * gg));
+  const unsigned long long bal = (__ballot(ok) >> shift) & 0xffffull;
+  const float spick = __shfl(sj, bal ? __ffsll(bal) - 1 : 0, W);
+  return bal ? spick : 0.f;
+}
+
 // KFS: the fused sparse sweep — ONE launch per sweep for the routed
 // nodes.  Evolution is measured in profiles/r02_sparse_sweep.md; the
 // current (v10) structure:
@@ -2861,15 +3085,8 @@ __device__ __forceinline__ int epre_len(const int* __restrict__ epre,
 //   * the 16-candidate trial phase runs on an (edge-slot × candidate)
 //     THREAD mapping — no wave-wide reductions;
 //   * one packed 3-value block reduction (gg, fs, ff).
-// LDS = bitmap K/32 words (+ a u16 prefix per word) + cap*(16|20) bytes:
+// LDS (kfs_layout) = bitmap + u16 prefix per word + cap*(16|20) bytes:
 // 21 KB at the headline K=5000 bf16 (7 blocks/CU), ~78 KB at K=25000 with the occupancy-aware cap.
-
-template <bool BF16>
-__device__ __forceinline__ float vget(unsigned short v);
-template <>
-__device__ __forceinline__ float vget<true>(unsigned short v) {
-  return __uint_as_float((u32)v << 16);
-}
 
 template <bool BF16>
 __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
@@ -2893,24 +3110,8 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
   const int wid = tid >> 6;
   const int nw = (K + 31) >> 5;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // layout: bmap[nw] u32 | gacc[cap] f32 | gS[cap] f32 | nidx[cap] u16 |
-  //         kS[cap] u16 | nval[cap] u16|f32 | fuS[cap] u16|f32
-  u32* bmap = reinterpret_cast<u32*>(smem);
-  float* gacc = reinterpret_cast<float*>(bmap + nw);
-  float* gS = gacc + cap;
-  unsigned short* nidx = reinterpret_cast<unsigned short*>(gS + cap);
-  unsigned short* kS = nidx + cap;
-  char* pv = reinterpret_cast<char*>(kS + cap);
-  float* nval_f = reinterpret_cast<float*>(pv);
-  unsigned short* nval_h = reinterpret_cast<unsigned short*>(pv);
-  pv += (size_t)cap * (BF16 ? 2 : 4);
-  pv = (char*)(((size_t)pv + 3) & ~(size_t)3);
-  float* fuS_f = reinterpret_cast<float*>(pv);
-  unsigned short* fuS_h = reinterpret_cast<unsigned short*>(pv);
-  // pref[nw] u16: per-bitmap-word exclusive prefix count (slot of a
-  // column = pref[word] + popcount of the word's lower bits)
-  unsigned short* pref = reinterpret_cast<unsigned short*>(
-      pv + (size_t)cap * (BF16 ? 2 : 4));
+  const SweepView<BF16> s(smem, kfs_layout(BF16, K, cap));
+  float* const gS = s.sfS;
   __shared__ int scan[NWAVE];
   __shared__ float s_lad[MAX_LS];
   __shared__ double cllh[16][MAX_LS];
@@ -2921,7 +3122,7 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
   __shared__ float sh_gg;
 
   if (tid < MAX_LS) s_lad[tid] = (tid < n_ladder) ? ladder[tid] : 0.f;
-  for (int i = tid; i < nw; i += BLOCK) bmap[i] = 0u;
+  for (int i = tid; i < nw; i += BLOCK) s.bmap[i] = 0u;
   __syncthreads();
 
   // phase 1: stage neighbor lists (wave-per-edge) + OR support bits
@@ -2930,36 +3131,20 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
   if (phases & 8)
   for (long long e = e0 + wid; e < e1; e += NWAVE) {
     const int v = indices[e];
-    const long long off = soffset[v];
-    const int sv = scount[v];
-    const int base = epre[e];
-    for (int j = lane; j < sv; j += WAVE) {
-      const int k = sidx[off + j];
-      nidx[base + j] = (unsigned short)k;
-      if (BF16)
-        nval_h[base + j] = pack1_bf16_rne(sval[off + j]);
-      else
-        nval_f[base + j] = sval[off + j];
-      atomicOr(&bmap[k >> 5], 1u << (k & 31));
-    }
+    stage_list<WAVE>(s, sidx, sval, soffset[v], epre[e], scount[v], lane);
   }
-  {  // own support bits
-    const long long offu = soffset[u];
-    const int su = scount[u];
-    for (int j = tid; j < su; j += BLOCK)
-      atomicOr(&bmap[sidx[offu + j] >> 5], 1u << (sidx[offu + j] & 31));
-  }
+  or_own_bits<BLOCK>(s, sidx, soffset[u], scount[u], tid);
   __syncthreads();
 
   // phase 1.5: bitmap scan -> sorted compact kS + fuS gather + gacc
   // slot zeroing; then transform the staged entries to SLOT POSITIONS
-  // (one binary search per entry) — no global gathers after this point
+  // (rank by popcount) — no global gathers after this point
   const int wchunk = (nw + BLOCK - 1) / BLOCK;
   const int w0 = min(tid * wchunk, nw);
   const int w1 = min(w0 + wchunk, nw);
   int cnt = 0;
   if (phases & 2)
-    for (int wv = w0; wv < w1; ++wv) cnt += __popc(bmap[wv]);
+    for (int wv = w0; wv < w1; ++wv) cnt += __popc(s.bmap[wv]);
   int incl = cnt;
 #pragma unroll
   for (int off = 1; off < WAVE; off <<= 1) {
@@ -2973,33 +3158,12 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
   for (int wv = 0; wv < NWAVE; ++wv)
     if (wv < wid) wbase += scan[wv];
   const int ns = scan[0] + scan[1] + scan[2] + scan[3];
-  int pos = wbase + incl - cnt;
-  for (int wv = w0; wv < w1; ++wv) {
-    u32 bits = bmap[wv];
-    pref[wv] = (unsigned short)pos;
-    while (bits) {
-      const int b = __ffs(bits) - 1;
-      bits &= bits - 1;
-      const int k = (wv << 5) + b;
-      kS[pos] = (unsigned short)k;
-      const float f = f_elem<BF16>(Fp, K, u, k);
-      if (BF16)
-        fuS_h[pos] = pack1_bf16_rne(f);
-      else
-        fuS_f[pos] = f;
-      gacc[pos] = 0.f;
-      ++pos;
-    }
-  }
+  emit_words(s, w0, w1, wbase + incl - cnt, [&](int pos, int k) {
+    s.set_fu(pos, f_elem<BF16>(Fp, K, u, k));
+    s.gacc[pos] = 0.f;
+  });
   __syncthreads();
-  {  // staged column ids -> compact positions, in place
-    for (int i = tid; i < total; i += BLOCK) {
-      const int k = (int)nidx[i];  // always present: k came from bmap
-      const int wv = k >> 5;
-      nidx[i] = (unsigned short)((int)pref[wv] +
-                                 __popc(bmap[wv] & ((1u << (k & 31)) - 1u)));
-    }
-  }
+  to_slots<BLOCK>(s, total, tid);
   __syncthreads();
 
   // phase 2: WAVE-per-edge dot (all operands in LDS) -> w-weighted LDS
@@ -3009,21 +3173,12 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
   for (long long e = e0 + wid; e < e1; e += NWAVE) {
     const int base = epre[e];
     const int sv = epre_len(epre, e, (int)(e - e0), deg, total);
-    float part = 0.f;
-    for (int j = lane; j < sv; j += WAVE) {
-      const int p_ = (int)nidx[base + j];
-      const float fv = BF16 ? vget<true>(nval_h[base + j]) : nval_f[base + j];
-      const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
-      part += fu * fv;
-    }
-    const float x = wave_allreduce_sum(part);
-    const float p = clamp_p(__expf(-x), min_p, max_p);
+    const float x = wave_allreduce_sum(list_dot<WAVE>(s, base, sv, lane));
+    const float p = edge_p(x, min_p, max_p);
     const float w = 1.f / (1.f - p);
-    if (lane == 0) llh_acc += (double)log1pf(-p) + (double)x;
-    for (int j = lane; j < sv; j += WAVE) {
-      const float fv = BF16 ? vget<true>(nval_h[base + j]) : nval_f[base + j];
-      atomicAdd(&gacc[nidx[base + j]], w * fv);
-    }
+    if (lane == 0) llh_acc += edge_term(p, x);
+    for (int j = lane; j < sv; j += WAVE)
+      atomicAdd(&s.gacc[s.nidx[base + j]], w * s.nval(base + j));
   }
   __syncthreads();
 
@@ -3031,18 +3186,8 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
   // node terms fs/ff and gg accumulate alongside
   const long long go = goffset[blockIdx.x];
   float gg_p = 0.f, fs_p = 0.f, ff_p = 0.f;
-  for (int i = tid; i < ns; i += BLOCK) {
-    const int k = (int)kS[i];
-    const float f = BF16 ? vget<true>(fuS_h[i]) : fuS_f[i];
-    const float sfk = sumF[k];
-    const float g = gacc[i] - sfk + f;
-    gS[i] = g;
-    gidx[go + i] = k;
-    gval[go + i] = g;
-    gg_p += g * g - sfk * sfk;
-    fs_p = fmaf(f, sfk, fs_p);
-    ff_p = fmaf(f, f, ff_p);
-  }
+  for (int i = tid; i < ns; i += BLOCK)
+    finalize_slot<false>(s, i, sumF, gidx, gval, go, gg_p, fs_p, ff_p);
   // one packed reduction round: (gg, fs, ff) + the llh doubles
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -3087,31 +3232,17 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
       const int ne = (int)min((long long)16, e1 - et);
       if (ej < ne && jc < n_ladder) {
         const long long e = et + ej;
-        const int base = epre[e];
-        const int sv = epre_len(epre, e, (int)(e - e0), deg, total);
-        float x = 0.f;
-        for (int t = 0; t < sv; ++t) {
-          const int p_ = (int)nidx[base + t];
-          const float fv =
-              BF16 ? vget<true>(nval_h[base + t]) : nval_f[base + t];
-          const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
-          const float c = __builtin_amdgcn_fmed3f(fmaf(sj, gS[p_], fu),
-                                                  min_f, max_f);
-          x = fmaf(c, fv, x);
-        }
-        const float p = clamp_p(__expf(-x), min_p, max_p);
-        myllh += (double)log1pf(-p) + (double)x;
+        myllh += trial_edge_term(
+            s, gS, epre[e], epre_len(epre, e, (int)(e - e0), deg, total), sj,
+            min_p, max_p, min_f, max_f);
       }
     }
     // node terms: thread (stripe=ej, j=jc) over strided elements
     float mynt = 0.f;
     if (jc < n_ladder) {
-      for (int i = ej; i < ns; i += 16) {
-        const float fu = BF16 ? vget<true>(fuS_h[i]) : fuS_f[i];
-        const float c = __builtin_amdgcn_fmed3f(fmaf(sj, gS[i], fu), min_f,
-                                                max_f);
-        mynt = fmaf(c, fu - sumF[kS[i]], mynt);
-      }
+      for (int i = ej; i < ns; i += 16)
+        mynt = trial_node_term(s, gS, i, sumF[s.kS[i]], sj, min_f, max_f,
+                               mynt);
     }
     cllh[ej][jc] = myllh;
     cnt16[ej][jc] = mynt;
@@ -3146,8 +3277,6 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
 //   * per-edge (base, count) pairs are computed once from epre and kept
 //     in LDS (first KFW_ECAP edges; later edges of a rare wide node
 //     re-read epre) — no prefix reads inside the phase loops;
-//   * staged column -> slot by RANK: per-word exclusive prefix + popcount
-//     of the lower bits (two LDS reads, no binary search);
 //   * own row values come from the node's support list (contiguous)
 //     rather than a per-column gather from the F row;
 //   * dots run 4 edges at a time on 16-lane groups, the scatter into gacc
@@ -3158,20 +3287,8 @@ __global__ void __launch_bounds__(BLOCK) kfs_sparse_t(
 //     phase's node terms; the finalized gradient overwrites gacc in place;
 //   * trials: lanes = 4 edge slots x 16 candidates, combined by
 //     __shfl_xor 16 then 32.
-// LDS = bitmap K/32 words + u16 prefix per word + wcap*(16|20) bytes +
-// the edge table: 5.3 KB at K=5000 bf16 with wcap=256.  Measured in
+// LDS (kfw_layout): 5.3 KB at K=5000 bf16 with wcap=256.  Measured in
 // profiles/r05_kfs_wave.md.
-
-#define KFW_ECAP 64
-
-// The llh term and every trial term of an edge whose neighbour list is
-// empty: the dot is 0.f whatever the step, so the term is this constant.
-// The same expression the edge loops evaluate at x = 0.f, on the same
-// inputs — bitwise the value they would recompute.
-__device__ __forceinline__ double empty_edge_term(float min_p, float max_p) {
-  const float x = 0.f;
-  return (double)log1pf(-clamp_p(__expf(-x), min_p, max_p)) + (double)x;
-}
 
 // SKIP (KFW and KFP): an edge with an empty neighbour list costs a
 // lane-parallel test, not a walk.  Edge tables live in lanes (lane e =
@@ -3206,72 +3323,56 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
   const int gl = lane & 15;   // lane in group == candidate
   const int nw = (K + 31) >> 5;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // layout: bmap[nw] u32 | gacc[wcap] f32 | sfS[wcap] f32 | ebs[ECAP] u32
-  //         | (fp32: nval[wcap] fuS[wcap]) | nidx[wcap] u16 | kS[wcap] u16
-  //         | pref[nw] u16 | (bf16: nval[wcap] fuS[wcap] u16)
-  u32* bmap = reinterpret_cast<u32*>(smem);
-  float* gacc = reinterpret_cast<float*>(bmap + nw);
-  float* sfS = gacc + wcap;
-  u32* ebs = reinterpret_cast<u32*>(sfS + wcap);
-  float* nval_f = reinterpret_cast<float*>(ebs + KFW_ECAP);
-  float* fuS_f = nval_f + wcap;
-  unsigned short* nidx = reinterpret_cast<unsigned short*>(
-      BF16 ? nval_f : fuS_f + wcap);
-  unsigned short* kS = nidx + wcap;
-  unsigned short* pref = kS + wcap;
-  unsigned short* nval_h = pref + ((nw + 1) & ~1);
-  unsigned short* fuS_h = nval_h + wcap;
+  const SweepView<BF16> s(smem, kfw_layout(BF16, K, wcap));
 
-  // edge table: (staging base << 16) | list length, from the node-local
-  // prefix
   const int bnd = bound[u];
   const int total = bnd - scount[u];  // staged entries
   // SKIP: nothing staged and no own support — the active set is empty,
   // every edge term is c0: no bitmap pass, no rank, no phase-3 loop
   const bool quick = SKIP && bnd == 0;
   const double c0 = empty_edge_term(min_p, max_p);
+  // edge i's table entry: (staging base << 16) | list length
+  auto entry = [&](int i) -> u32 {
+    return ((u32)epre[e0 + i] << 16) |
+           (u32)epre_len(epre, e0 + i, i, deg, total);
+  };
   u32 bs0 = 0u;  // SKIP: lane e keeps edge e's entry (first 64 edges)
   if (!quick) {
     if (lane < deg) {  // KFW_ECAP == WAVE: one pass
-      bs0 = ((u32)epre[e0 + lane] << 16) |
-            (u32)epre_len(epre, e0 + lane, lane, deg, total);
-      if (!SKIP) ebs[lane] = bs0;
+      bs0 = entry(lane);
+      if (!SKIP) s.ebs[lane] = bs0;
     }
-    for (int i = lane; i < nw; i += WAVE) bmap[i] = 0u;
+    for (int i = lane; i < nw; i += WAVE) s.bmap[i] = 0u;
     __syncthreads();
   }
   auto edge_bs = [&](int i) -> u32 {
-    if (i < KFW_ECAP) return ebs[i];
-    return ((u32)epre[e0 + i] << 16) |
-           (u32)epre_len(epre, e0 + i, i, deg, total);
+    return i < KFW_ECAP ? s.ebs[i] : entry(i);
   };
   // SKIP: the entries of edges c .. c+63, one per lane (one coalesced
   // epre read per 64 edges past the first chunk); 0 past the degree
   auto chunk_bs = [&](int c) -> u32 {
     if (c == 0) return bs0;
-    const int i = c + lane;
-    return i < deg ? ((u32)epre[e0 + i] << 16) |
-                         (u32)epre_len(epre, e0 + i, i, deg, total)
-                   : 0u;
+    return c + lane < deg ? entry(c + lane) : 0u;
+  };
+
+  // SKIP: takes the next four set bits off m, ascending, into idx (-1 once
+  // m runs out); returns the one of this lane's group
+  auto next4 = [&](unsigned long long& m, int (&idx)[4]) -> int {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      idx[r] = m ? __ffsll(m) - 1 : -1;
+      m &= m - 1;  // 0 stays 0
+    }
+    return grp == 0 ? idx[0] : grp == 1 ? idx[1] : grp == 2 ? idx[2] : idx[3];
   };
 
   // phase 1: stage neighbour lists, 4 edges at a time (16 lanes per
   // edge), OR support bits
   auto stage_edge = [&](int ei, u32 bs) {
-    const int base = (int)(bs >> 16);
     const int sv = (int)(bs & 0xffffu);
-    if (sv) {
-      const long long off = soffset[indices[e0 + ei]];
-      for (int j = gl; j < sv; j += 16) {
-        const int k = sidx[off + j];
-        nidx[base + j] = (unsigned short)k;
-        if (BF16)
-          nval_h[base + j] = pack1_bf16_rne(sval[off + j]);
-        else
-          nval_f[base + j] = sval[off + j];
-        atomicOr(&bmap[k >> 5], 1u << (k & 31));
-      }
-    }
+    if (sv)
+      stage_list<16>(s, sidx, sval, soffset[indices[e0 + ei]],
+                     (int)(bs >> 16), sv, gl);
   };
   if (SKIP) {
     // the non-empty edges of each chunk, four set bits at a time
@@ -3279,14 +3380,8 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
       const u32 bs_l = chunk_bs(c);
       unsigned long long m = __ballot((bs_l & 0xffffu) != 0u);
       while (m) {
-        int mine = -1;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (m) {
-            if (grp == r) mine = __ffsll(m) - 1;
-            m &= m - 1;
-          }
-        }
+        int idx[4];
+        const int mine = next4(m, idx);
         const u32 bs = __shfl(bs_l, mine < 0 ? 0 : mine, WAVE);
         if (mine >= 0) stage_edge(c + mine, bs);
       }
@@ -3301,61 +3396,15 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
   const int su = scount[u];
   int ns = 0;
   if (!quick) {
-    for (int j = lane; j < su; j += WAVE) {
-      const int k = sidx[offu + j];
-      atomicOr(&bmap[k >> 5], 1u << (k & 31));
-    }
+    or_own_bits<WAVE>(s, sidx, offu, su, lane);
     __syncthreads();
-
     // phase 1.5: bitmap scan -> sorted compact kS, per-word exclusive
-    // prefix, zeroed gacc/fuS slots
-    const int wchunk = (nw + WAVE - 1) / WAVE;
-    const int w0 = min(lane * wchunk, nw);
-    const int w1 = min(w0 + wchunk, nw);
-    int cnt = 0;
-    for (int wv = w0; wv < w1; ++wv) cnt += __popc(bmap[wv]);
-    int incl = cnt;
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) {
-      const int v = __shfl_up(incl, off, WAVE);
-      if (lane >= off) incl += v;
-    }
-    ns = __shfl(incl, WAVE - 1, WAVE);
-    {
-      int pos = incl - cnt;
-      for (int wv = w0; wv < w1; ++wv) {
-        u32 bits = bmap[wv];
-        pref[wv] = (unsigned short)pos;
-        while (bits) {
-          const int bb = __ffs(bits) - 1;
-          bits &= bits - 1;
-          kS[pos] = (unsigned short)((wv << 5) + bb);
-          if (BF16)
-            fuS_h[pos] = 0;
-          else
-            fuS_f[pos] = 0.f;
-          gacc[pos] = 0.f;
-          ++pos;
-        }
-      }
-    }
+    // prefix, zeroed gacc/fuS slots; then own row values and the staged
+    // columns to their slots
+    ns = bitmap_scan<WAVE>(s, nw, lane);
     __syncthreads();
-    auto rank_of = [&](int k) -> int {
-      const int wv = k >> 5;
-      return (int)pref[wv] + __popc(bmap[wv] & ((1u << (k & 31)) - 1u));
-    };
-    // own row values into their slots (from the node's own support list)
-    for (int j = lane; j < su; j += WAVE) {
-      const int p_ = rank_of(sidx[offu + j]);
-      if (BF16)
-        fuS_h[p_] = pack1_bf16_rne(sval[offu + j]);
-      else
-        fuS_f[p_] = sval[offu + j];
-    }
-    {  // staged column ids -> slot positions, in place
-      for (int i = lane; i < total; i += WAVE)
-        nidx[i] = (unsigned short)rank_of((int)nidx[i]);
-    }
+    own_values<WAVE>(s, sidx, sval, offu, su, lane);
+    to_slots<WAVE>(s, total, lane);
     __syncthreads();
   }
 
@@ -3385,38 +3434,19 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
       float x = 0.f;
       for (unsigned long long m = mask; m;) {
         int idx[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          idx[r] = m ? __ffsll(m) - 1 : -1;
-          m &= m - 1;  // 0 stays 0
-        }
-        const int mine = grp == 0   ? idx[0]
-                         : grp == 1 ? idx[1]
-                         : grp == 2 ? idx[2]
-                                    : idx[3];
+        const int mine = next4(m, idx);
         const u32 bs = __shfl(bs_l, mine < 0 ? 0 : mine, WAVE);
-        const int base = (int)(bs >> 16);
-        const int sv = mine < 0 ? 0 : (int)(bs & 0xffffu);
-        float part = 0.f;
-        for (int j = gl; j < sv; j += 16) {
-          const int p_ = (int)nidx[base + j];
-          const float fv =
-              BF16 ? vget<true>(nval_h[base + j]) : nval_f[base + j];
-          const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
-          part += fu * fv;
-        }
-#pragma unroll
-        for (int off = 8; off > 0; off >>= 1)
-          part += __shfl_xor(part, off, WAVE);
+        const float part = group_dot(s, (int)(bs >> 16),
+                                     mine < 0 ? 0 : (int)(bs & 0xffffu), gl);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float xr = __shfl(part, r << 4, WAVE);
           if (lane == idx[r]) x = xr;
         }
       }
-      const float p = clamp_p(__expf(-x), min_p, max_p);
+      const float p = edge_p(x, min_p, max_p);
       const float w = 1.f / (1.f - p);
-      const double term = (double)log1pf(-p) + (double)x;
+      const double term = edge_term(p, x);
       const int nch = min(WAVE, deg - c);
       for (int t = 0; t < nch; t += 4) {
         const int src = t + (lane & 3);
@@ -3427,13 +3457,7 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
         const int e = __ffsll(m) - 1;
         const u32 bs = __shfl(bs_l, e, WAVE);
         const float wq = __shfl(w, e, WAVE);
-        const int bq = (int)(bs >> 16);
-        const int sq = (int)(bs & 0xffffu);
-        for (int j = lane; j < sq; j += WAVE) {
-          const int p_ = (int)nidx[bq + j];
-          const float fv = BF16 ? vget<true>(nval_h[bq + j]) : nval_f[bq + j];
-          gacc[p_] += wq * fv;
-        }
+        list_scatter<WAVE>(s, (int)(bs >> 16), (int)(bs & 0xffffu), wq, lane);
       }
     }
     cls = __shfl(acc, grp, WAVE);  // lane q < 4 carries class q
@@ -3441,36 +3465,17 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
   if (SKIP && gl == 0) llh_acc = cls;
   for (int et = 0; et < deg && !SKIP; et += 4) {
     const int ei = et + grp;
-    int base = 0, sv = 0;
-    if (ei < deg) {
-      const u32 bs = edge_bs(ei);
-      base = (int)(bs >> 16);
-      sv = (int)(bs & 0xffffu);
-    }
-    float part = 0.f;
-    for (int j = gl; j < sv; j += 16) {
-      const int p_ = (int)nidx[base + j];
-      const float fv = BF16 ? vget<true>(nval_h[base + j]) : nval_f[base + j];
-      const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
-      part += fu * fv;
-    }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) part += __shfl_xor(part, off, WAVE);
-    const float x = part;
-    const float p = clamp_p(__expf(-x), min_p, max_p);
+    const u32 bs = ei < deg ? edge_bs(ei) : 0u;  // past the degree: empty
+    const int base = (int)(bs >> 16), sv = (int)(bs & 0xffffu);
+    const float x = group_dot(s, base, sv, gl);
+    const float p = edge_p(x, min_p, max_p);
     const float w = 1.f / (1.f - p);
-    if (ei < deg && gl == 0) llh_acc += (double)log1pf(-p) + (double)x;
+    if (ei < deg && gl == 0) llh_acc += edge_term(p, x);
     const int nq = min(4, deg - et);
-    for (int q = 0; q < nq; ++q) {
-      const int bq = __shfl(base, q << 4, WAVE);
-      const int sq = __shfl(sv, q << 4, WAVE);
-      const float wq = __shfl(w, q << 4, WAVE);
-      for (int j = lane; j < sq; j += WAVE) {
-        const int p_ = (int)nidx[bq + j];
-        const float fv = BF16 ? vget<true>(nval_h[bq + j]) : nval_f[bq + j];
-        gacc[p_] += wq * fv;
-      }
-    }
+    for (int q = 0; q < nq; ++q)
+      list_scatter<WAVE>(s, __shfl(base, q << 4, WAVE),
+                         __shfl(sv, q << 4, WAVE), __shfl(w, q << 4, WAVE),
+                         lane);
   }
   __syncthreads();
 
@@ -3478,19 +3483,8 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
   // pools; node terms fs/ff and gg accumulate alongside
   const long long go = goffset[b];
   float gg_p = 0.f, fs_p = 0.f, ff_p = 0.f;
-  for (int i = lane; i < ns; i += WAVE) {
-    const int k = (int)kS[i];
-    const float f = BF16 ? vget<true>(fuS_h[i]) : fuS_f[i];
-    const float sfk = sumF[k];
-    const float g = gacc[i] - sfk + f;
-    gacc[i] = g;
-    sfS[i] = sfk;
-    gidx[go + i] = k;
-    gval[go + i] = g;
-    gg_p += g * g - sfk * sfk;
-    fs_p = fmaf(f, sfk, fs_p);
-    ff_p = fmaf(f, f, ff_p);
-  }
+  for (int i = lane; i < ns; i += WAVE)
+    finalize_slot<true>(s, i, sumF, gidx, gval, go, gg_p, fs_p, ff_p);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     gg_p += __shfl_xor(gg_p, off, WAVE);
@@ -3512,19 +3506,8 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
   const float sj = live ? ladder[gl] : 0.f;
   double myllh = 0.0;
   auto trial_edge = [&](u32 bs) {
-    const int base = (int)(bs >> 16);
-    const int sv = (int)(bs & 0xffffu);
-    float x = 0.f;
-    for (int t = 0; t < sv; ++t) {
-      const int p_ = (int)nidx[base + t];
-      const float fv = BF16 ? vget<true>(nval_h[base + t]) : nval_f[base + t];
-      const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
-      const float c =
-          __builtin_amdgcn_fmed3f(fmaf(sj, gacc[p_], fu), min_f, max_f);
-      x = fmaf(c, fv, x);
-    }
-    const float p = clamp_p(__expf(-x), min_p, max_p);
-    myllh += (double)log1pf(-p) + (double)x;
+    myllh += trial_edge_term(s, s.gacc, (int)(bs >> 16), (int)(bs & 0xffffu),
+                             sj, min_p, max_p, min_f, max_f);
   };
   if (SKIP && quick) {
     if (live) myllh = cls;  // 0.0 + c0 + c0 ..., the chain of phase 4
@@ -3551,22 +3534,16 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
   }
   float mynt = 0.f;
   if (live) {
-    for (int i = grp; i < ns; i += 4) {
-      const float fu = BF16 ? vget<true>(fuS_h[i]) : fuS_f[i];
-      const float c =
-          __builtin_amdgcn_fmed3f(fmaf(sj, gacc[i], fu), min_f, max_f);
-      mynt = fmaf(c, fu - sfS[i], mynt);
-    }
+    for (int i = grp; i < ns; i += 4)
+      mynt = trial_node_term(s, s.gacc, i, s.sfS[i], sj, min_f, max_f, mynt);
   }
   myllh += __shfl_xor(myllh, 16, WAVE);
   mynt += __shfl_xor(mynt, 16, WAVE);
   myllh += __shfl_xor(myllh, 32, WAVE);
   mynt += __shfl_xor(mynt, 32, WAVE);
-  const bool ok = live && (myllh + (double)mynt >=
-                           llh_base + (double)(alpha * sj * gg));
-  const unsigned long long bal = __ballot(ok) & 0xffffull;
-  const float spick = __shfl(sj, bal ? __ffsll(bal) - 1 : 0, WAVE);
-  if (lane == 0) best[u] = bal ? spick : 0.f;
+  const float pick =
+      armijo_pick<WAVE>(live, myllh, mynt, llh_base, alpha, sj, gg, 0);
+  if (lane == 0) best[u] = pick;
 }
 
 // KFP: the KFW computation with FOUR nodes per wave, 16 lanes per node,
@@ -3595,24 +3572,8 @@ __global__ void __launch_bounds__(WAVE) kfw_sparse_t(
 //     and node terms i = q (mod 4), folded by xor 16 then 32 =
 //     (m0 + m1) + (m2 + m3); lane (node, candidate) here walks the node's
 //     edges serially with four accumulators and folds the same way.
-// LDS = four bitmaps (nw rounded up to 4 words, cleared with 16-byte
-// stores) + per node: u16 prefix per word, qcap*(16|20) bytes, a 16-entry
-// edge table: 8 KB at K=5000 bf16 with qcap=64.  Measured in
+// LDS (kfp_layout): 8 KB at K=5000 bf16 with qcap=64.  Measured in
 // profiles/r08_kfp_pack.md.
-
-#define KFP_NODES 4   // nodes per wave
-
-// bitmap words per node, rounded so the four bitmaps clear as uint4
-__host__ __device__ __forceinline__ int kfp_nwp(int K) {
-  return (((K + 31) >> 5) + 3) & ~3;
-}
-// bytes of one node's private region after the bitmaps (q4 = qcap rounded
-// up to 4): gacc, sfS f32 | ebs[16] u32 | (fp32: nval, fuS f32) | nidx, kS
-// u16 | pref[nwp] u16 | (bf16: nval, fuS u16); a multiple of 16
-__host__ __device__ __forceinline__ int kfp_node_bytes(bool bf16, int nwp,
-                                                       int q4) {
-  return (q4 * (bf16 ? 16 : 20) + KFP_DEG * 4 + nwp * 2 + 15) & ~15;
-}
 
 template <bool BF16, bool SKIP>
 __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
@@ -3632,8 +3593,6 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
   const int grp = lane >> 4;  // node of the quad
   const int gl = lane & 15;   // lane in group == edge == candidate
   const int nw = (K + 31) >> 5;
-  const int nwp = kfp_nwp(K);
-  const int q4 = (qcap + 3) & ~3;
   const int slot = KFP_NODES * (int)blockIdx.x + grp;
   const bool alive = slot < n_pack;
   const int b = pos[alive ? slot : n_pack - 1];  // position, routed order
@@ -3651,20 +3610,8 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
   const int total = fits ? bnd - su_u : 0;  // staged entries
   const long long offu = soffset[u];
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  u32* bmap = reinterpret_cast<u32*>(smem) + grp * nwp;
-  char* reg = smem + (size_t)KFP_NODES * nwp * 4 +
-              (size_t)grp * kfp_node_bytes(BF16, nwp, q4);
-  float* gacc = reinterpret_cast<float*>(reg);
-  float* sfS = gacc + q4;
-  u32* ebs = reinterpret_cast<u32*>(sfS + q4);
-  float* nval_f = reinterpret_cast<float*>(ebs + KFP_DEG);
-  float* fuS_f = nval_f + q4;
-  unsigned short* nidx = reinterpret_cast<unsigned short*>(
-      BF16 ? nval_f : fuS_f + q4);
-  unsigned short* kS = nidx + q4;
-  unsigned short* pref = kS + q4;
-  unsigned short* nval_h = pref + nwp;
-  unsigned short* fuS_h = nval_h + q4;
+  const SweepLds lay = kfp_layout(BF16, K, qcap, grp);
+  const SweepView<BF16> s(smem, lay);
 
   // lane e holds edge e of its node: (staging base << 16) | list length
   // and the neighbour's list offset; 0 past the degree (an empty edge)
@@ -3700,10 +3647,12 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
   };
   int ns = 0;
   if (!quick) {
-    ebs[gl] = bs_l;  // the trial phase indexes edges per lane
+    s.ebs[gl] = bs_l;  // the trial phase indexes edges per lane
     {
-      uint4* bm4 = reinterpret_cast<uint4*>(smem);  // 4 bitmaps = nwp uint4
-      for (int i = lane; i < nwp; i += WAVE) bm4[i] = make_uint4(0, 0, 0, 0);
+      // the four bitmaps, lay.nbm words each, clear as lay.nbm uint4
+      uint4* bm4 = reinterpret_cast<uint4*>(smem);
+      for (int i = lane; i < lay.nbm; i += WAVE)
+        bm4[i] = make_uint4(0, 0, 0, 0);
     }
     __syncthreads();
 
@@ -3711,70 +3660,18 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
     for_edges([&](int e) {
       const u32 bs = __shfl(bs_l, e, 16);
       const long long off = __shfl(off_l, e, 16);
-      const int base = (int)(bs >> 16);
-      const int sv = (int)(bs & 0xffffu);
-      for (int j = gl; j < sv; j += 16) {
-        const int k = sidx[off + j];
-        nidx[base + j] = (unsigned short)k;
-        if (BF16)
-          nval_h[base + j] = pack1_bf16_rne(sval[off + j]);
-        else
-          nval_f[base + j] = sval[off + j];
-        atomicOr(&bmap[k >> 5], 1u << (k & 31));
-      }
+      stage_list<16>(s, sidx, sval, off, (int)(bs >> 16),
+                     (int)(bs & 0xffffu), gl);
     });
-    for (int j = gl; j < su; j += 16) {
-      const int k = sidx[offu + j];
-      atomicOr(&bmap[k >> 5], 1u << (k & 31));
-    }
+    or_own_bits<16>(s, sidx, offu, su, gl);
     __syncthreads();
-
     // phase 1.5: bitmap scan over the group's 16 lanes -> sorted compact
-    // kS, per-word exclusive prefix, zeroed gacc/fuS slots
-    const int wchunk = (nw + 15) >> 4;
-    const int w0 = min(gl * wchunk, nw);
-    const int w1 = min(w0 + wchunk, nw);
-    int cnt = 0;
-    for (int wv = w0; wv < w1; ++wv) cnt += __popc(bmap[wv]);
-    int incl = cnt;
-#pragma unroll
-    for (int off = 1; off < 16; off <<= 1) {
-      const int v = __shfl_up(incl, off, 16);
-      if (gl >= off) incl += v;
-    }
-    ns = __shfl(incl, 15, 16);
-    if (cnt) {
-      int p_ = incl - cnt;
-      for (int wv = w0; wv < w1; ++wv) {
-        u32 bits = bmap[wv];
-        pref[wv] = (unsigned short)p_;
-        while (bits) {
-          const int bb = __ffs(bits) - 1;
-          bits &= bits - 1;
-          kS[p_] = (unsigned short)((wv << 5) + bb);
-          if (BF16)
-            fuS_h[p_] = 0;
-          else
-            fuS_f[p_] = 0.f;
-          gacc[p_] = 0.f;
-          ++p_;
-        }
-      }
-    }
+    // kS, per-word exclusive prefix, zeroed gacc/fuS slots; then own row
+    // values and the staged columns to their slots
+    ns = bitmap_scan<16>(s, nw, gl);
     __syncthreads();
-    auto rank_of = [&](int k) -> int {
-      const int wv = k >> 5;
-      return (int)pref[wv] + __popc(bmap[wv] & ((1u << (k & 31)) - 1u));
-    };
-    for (int j = gl; j < su; j += 16) {
-      const int p_ = rank_of(sidx[offu + j]);
-      if (BF16)
-        fuS_h[p_] = pack1_bf16_rne(sval[offu + j]);
-      else
-        fuS_f[p_] = sval[offu + j];
-    }
-    for (int i = gl; i < total; i += 16)
-      nidx[i] = (unsigned short)rank_of((int)nidx[i]);
+    own_values<16>(s, sidx, sval, offu, su, gl);
+    to_slots<16>(s, total, gl);
     __syncthreads();
   }
 
@@ -3784,25 +3681,15 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
   float x = 0.f;
   for_edges([&](int e) {
     const u32 bs = __shfl(bs_l, e, 16);
-    const int base = (int)(bs >> 16);
-    const int sv = (int)(bs & 0xffffu);
-    float part = 0.f;
-    for (int j = gl; j < sv; j += 16) {
-      const int p_ = (int)nidx[base + j];
-      const float fv = BF16 ? vget<true>(nval_h[base + j]) : nval_f[base + j];
-      const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
-      part += fu * fv;
-    }
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) part += __shfl_xor(part, off, WAVE);
+    const float part = group_dot(s, (int)(bs >> 16), (int)(bs & 0xffffu), gl);
     if (gl == e) x = part;
   });
-  const float p = clamp_p(__expf(-x), min_p, max_p);
+  const float p = edge_p(x, min_p, max_p);
   const float w = 1.f / (1.f - p);
   double llh_acc;
   {
     double le = 0.0;
-    if (gl < deg) le += (double)log1pf(-p) + (double)x;
+    if (gl < deg) le += edge_term(p, x);
     double t = le + __shfl_down(le, 4, 16);
     t += __shfl_down(le, 8, 16);
     t += __shfl_down(le, 12, 16);          // lane q < 4: A_q
@@ -3812,13 +3699,7 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
   for_edges([&](int e) {
     const u32 bs = __shfl(bs_l, e, 16);
     const float wq = __shfl(w, e, 16);
-    const int bq = (int)(bs >> 16);
-    const int sq = (int)(bs & 0xffffu);
-    for (int j = gl; j < sq; j += 16) {
-      const int p_ = (int)nidx[bq + j];
-      const float fv = BF16 ? vget<true>(nval_h[bq + j]) : nval_f[bq + j];
-      gacc[p_] += wq * fv;
-    }
+    list_scatter<16>(s, (int)(bs >> 16), (int)(bs & 0xffffu), wq, gl);
   });
   __syncthreads();
 
@@ -3832,19 +3713,9 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int i = i0 + 16 * q;
-      if (i < ns) {
-        const int k = (int)kS[i];
-        const float f = BF16 ? vget<true>(fuS_h[i]) : fuS_f[i];
-        const float sfk = sumF[k];
-        const float g = gacc[i] - sfk + f;
-        gacc[i] = g;
-        sfS[i] = sfk;
-        gidx[go + i] = k;
-        gval[go + i] = g;
-        gg_c[q] += g * g - sfk * sfk;
-        fs_c[q] = fmaf(f, sfk, fs_c[q]);
-        ff_c[q] = fmaf(f, f, ff_c[q]);
-      }
+      if (i < ns)
+        finalize_slot<true>(s, i, sumF, gidx, gval, go, gg_c[q], fs_c[q],
+                            ff_c[q]);
     }
   }
   float gg_p = (gg_c[0] + gg_c[2]) + (gg_c[1] + gg_c[3]);
@@ -3877,21 +3748,10 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
         if (SKIP && et + q < deg && !((gm >> (et + q)) & 1u)) {
           m[q] += c0;  // empty edge: the term at x = 0.f, same chain
         } else if (et + q < deg) {
-          const u32 bs = ebs[et + q];
-          const int base = (int)(bs >> 16);
-          const int sv = (int)(bs & 0xffffu);
-          float xt = 0.f;
-          for (int t = 0; t < sv; ++t) {
-            const int p_ = (int)nidx[base + t];
-            const float fv =
-                BF16 ? vget<true>(nval_h[base + t]) : nval_f[base + t];
-            const float fu = BF16 ? vget<true>(fuS_h[p_]) : fuS_f[p_];
-            const float c =
-                __builtin_amdgcn_fmed3f(fmaf(sj, gacc[p_], fu), min_f, max_f);
-            xt = fmaf(c, fv, xt);
-          }
-          const float pt = clamp_p(__expf(-xt), min_p, max_p);
-          m[q] += (double)log1pf(-pt) + (double)xt;
+          const u32 bs = s.ebs[et + q];
+          m[q] += trial_edge_term(s, s.gacc, (int)(bs >> 16),
+                                  (int)(bs & 0xffffu), sj, min_p, max_p,
+                                  min_f, max_f);
         }
       }
     }
@@ -3899,22 +3759,17 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int i = i0 + q;
-        if (i < ns) {
-          const float fu = BF16 ? vget<true>(fuS_h[i]) : fuS_f[i];
-          const float c =
-              __builtin_amdgcn_fmed3f(fmaf(sj, gacc[i], fu), min_f, max_f);
-          nt[q] = fmaf(c, fu - sfS[i], nt[q]);
-        }
+        if (i < ns)
+          nt[q] = trial_node_term(s, s.gacc, i, s.sfS[i], sj, min_f, max_f,
+                                  nt[q]);
       }
     }
   }
   const double myllh = (m[0] + m[1]) + (m[2] + m[3]);
   const float mynt = (nt[0] + nt[1]) + (nt[2] + nt[3]);
-  const bool ok = live && (myllh + (double)mynt >=
-                           llh_base + (double)(alpha * sj * gg));
-  const unsigned long long bal = (__ballot(ok) >> (grp * 16)) & 0xffffull;
-  const float spick = __shfl(sj, bal ? __ffsll(bal) - 1 : 0, 16);
-  if (gl == 0 && alive) best[u] = bal ? spick : 0.f;
+  const float pick =
+      armijo_pick<16>(live, myllh, mynt, llh_base, alpha, sj, gg, grp * 16);
+  if (gl == 0 && alive) best[u] = pick;
 }
 
 // K3S also REWRITES the committed row's persistent support list
@@ -4748,77 +4603,56 @@ extern "C" void launch_kaf(const void* F, int bf16, int n_rows, int K,
   HIP_CHECK(hipGetLastError());
 }
 
-extern "C" void launch_kfs(const void* F, int bf16,
-                           const long long* indptr, const int* indices,
-                           const float* sumF, const int* order, int n_blocks,
-                           const long long* soffset, const int* sidx,
-                           const float* sval, const int* scount,
-                           const int* epre, const int* bound,
-                           const long long* goffset,
-                           int* gidx, float* gval, int* gcount, double* llh,
-                           const float* GGp, const float* ladder,
-                           float* best, int n_ladder, int cap, int K,
-                           float alpha, float min_p, float max_p,
-                           float min_f, float max_f, hipStream_t stream) {
+// what every sweep kernel takes after its own leading arguments, in
+// signature order up to n_ladder; the slot cap and the clamps follow
+#define SWEEP_SHARED(a)                                                    \
+  (a).soffset, (a).sidx, (a).sval, (a).scount, (a).epre, (a).bound,        \
+      (a).goffset, (a).gidx, (a).gval, (a).gcount, (a).llh, (a).GG,        \
+      (a).ladder, (a).best, (a).n_ladder
+#define SWEEP_CLAMPS(a) (a).alpha, (a).min_p, (a).max_p, (a).min_f, (a).max_f
+
+extern "C" void launch_kfs(const SweepArgs& a, const void* F, int bf16,
+                           int n_blocks, int cap, hipStream_t stream) {
   if (n_blocks == 0) return;
-  if (n_ladder > 16) throw std::runtime_error("ladder length > 16 unsupported");
-  const size_t lds = ((K + 31) / 32) * 6 + (size_t)cap * (bf16 ? 16 : 20)
-                     + 16;
+  if (a.n_ladder > 16)
+    throw std::runtime_error("ladder length > 16 unsupported");
+  const size_t lds = (size_t)kfs_layout(bf16 != 0, a.K, cap).total;
   const char* ph = getenv("BIGCLAM_KFS_PHASES");  // measurement bisect only
   const int phases = ph ? atoi(ph) : 0xF;
-  if (bf16) {
-    allow_large_lds((const void*)&kfs_sparse_t<true>, lds);
-    hipLaunchKernelGGL((kfs_sparse_t<true>), dim3(n_blocks), dim3(BLOCK),
-                       lds, stream, F, K, indptr, indices, sumF, order,
-                       soffset, sidx, sval, scount, epre, bound, goffset, gidx,
-                       gval, gcount, llh, GGp, ladder, best, n_ladder, cap,
-                       alpha, min_p, max_p, min_f, max_f, phases);
-  } else {
-    allow_large_lds((const void*)&kfs_sparse_t<false>, lds);
-    hipLaunchKernelGGL((kfs_sparse_t<false>), dim3(n_blocks), dim3(BLOCK),
-                       lds, stream, F, K, indptr, indices, sumF, order,
-                       soffset, sidx, sval, scount, epre, bound, goffset, gidx,
-                       gval, gcount, llh, GGp, ladder, best, n_ladder, cap,
-                       alpha, min_p, max_p, min_f, max_f, phases);
-  }
+#define KFS_LAUNCH(BF)                                                      \
+  do {                                                                      \
+    allow_large_lds((const void*)&kfs_sparse_t<BF>, lds);                   \
+    hipLaunchKernelGGL((kfs_sparse_t<BF>), dim3(n_blocks), dim3(BLOCK),     \
+                       lds, stream, F, a.K, a.indptr, a.indices, a.sumF,    \
+                       a.order, SWEEP_SHARED(a), cap, SWEEP_CLAMPS(a),      \
+                       phases);                                             \
+  } while (0)
+  if (bf16) KFS_LAUNCH(true); else KFS_LAUNCH(false);
+#undef KFS_LAUNCH
   HIP_CHECK(hipGetLastError());
 }
 
-// KFW LDS bytes for (K, wcap): bitmap + u16 prefix + wcap*(16|20) + the
-// edge table.  Exposed so the host clamps wcap to the workgroup budget.
+// Exposed so the host clamps wcap to the workgroup budget.
 extern "C" long long kfw_lds_bytes(int bf16, int K, int wcap) {
-  const long long nw = (K + 31) / 32;
-  return nw * 4 + ((nw + 1) & ~1LL) * 2 + (long long)wcap * (bf16 ? 16 : 20) +
-         KFW_ECAP * 4;
+  return kfw_layout(bf16 != 0, K, wcap).total;
 }
 
-extern "C" void launch_kfw(int bf16, const long long* indptr,
-                           const int* indices, const float* sumF,
-                           const int* order, int blk0, const int* pos,
-                           int n_blocks,
-                           const long long* soffset, const int* sidx,
-                           const float* sval, const int* scount,
-                           const int* epre, const int* bound,
-                           const long long* goffset,
-                           int* gidx, float* gval, int* gcount, double* llh,
-                           const float* GGp, const float* ladder,
-                           float* best, int n_ladder, int wcap, int K,
-                           float alpha, float min_p, float max_p,
-                           float min_f, float max_f, int skip,
+extern "C" void launch_kfw(const SweepArgs& a, int bf16, int blk0,
+                           const int* pos, int n_blocks, int wcap, int skip,
                            hipStream_t stream) {
   if (n_blocks == 0) return;
-  if (n_ladder > 16) throw std::runtime_error("ladder length > 16 unsupported");
-  const size_t lds = (size_t)kfw_lds_bytes(bf16, K, wcap);
+  if (a.n_ladder > 16)
+    throw std::runtime_error("ladder length > 16 unsupported");
+  const size_t lds = (size_t)kfw_lds_bytes(bf16, a.K, wcap);
   if (lds > 160 * 1024)
     throw std::runtime_error("KFW: wcap exceeds the workgroup LDS budget");
 #define KFW_LAUNCH(BF, SK)                                                  \
   do {                                                                      \
     allow_large_lds((const void*)&kfw_sparse_t<BF, SK>, lds);               \
     hipLaunchKernelGGL((kfw_sparse_t<BF, SK>), dim3(n_blocks), dim3(WAVE),  \
-                       lds, stream, K, indptr, indices, sumF, order, blk0,  \
-                       pos, soffset, sidx, sval, scount, epre, bound,       \
-                       goffset, gidx, gval, gcount, llh, GGp, ladder, best, \
-                       n_ladder, wcap, alpha, min_p, max_p, min_f, max_f);  \
+                       lds, stream, a.K, a.indptr, a.indices, a.sumF,       \
+                       a.order, blk0, pos, SWEEP_SHARED(a), wcap,           \
+                       SWEEP_CLAMPS(a));                                    \
   } while (0)
   if (bf16) {
     if (skip) KFW_LAUNCH(true, true); else KFW_LAUNCH(true, false);
@@ -4829,43 +4663,27 @@ extern "C" void launch_kfw(int bf16, const long long* indptr,
   HIP_CHECK(hipGetLastError());
 }
 
-// KFP LDS bytes for (K, qcap): four bitmaps + per node (u16 prefix +
-// qcap*(16|20) + the 16-entry edge table).  Exposed so the host clamps
-// qcap to the workgroup budget.
+// Exposed so the host clamps qcap to the workgroup budget.
 extern "C" long long kfp_lds_bytes(int bf16, int K, int qcap) {
-  const int nwp = kfp_nwp(K);
-  return (long long)KFP_NODES *
-         (nwp * 4 + kfp_node_bytes(bf16 != 0, nwp, (qcap + 3) & ~3));
+  return kfp_layout(bf16 != 0, K, qcap).total;
 }
 
 extern "C" int kfp_deg() { return KFP_DEG; }
 
-// KFP over the pack positions pos[0 .. n_pack), four per workgroup
-extern "C" void launch_kfp(int bf16, const long long* indptr,
-                           const int* indices, const float* sumF,
-                           const int* order, const int* pos, int n_pack,
-                           const long long* soffset, const int* sidx,
-                           const float* sval, const int* scount,
-                           const int* epre, const int* bound,
-                           const long long* goffset,
-                           int* gidx, float* gval, int* gcount, double* llh,
-                           const float* GGp, const float* ladder,
-                           float* best, int n_ladder, int qcap, int K,
-                           float alpha, float min_p, float max_p,
-                           float min_f, float max_f, int skip,
+extern "C" void launch_kfp(const SweepArgs& a, int bf16, const int* pos,
+                           int n_pack, int qcap, int skip,
                            hipStream_t stream) {
   if (n_pack == 0) return;
-  if (n_ladder > 16) throw std::runtime_error("ladder length > 16 unsupported");
-  const size_t lds = (size_t)kfp_lds_bytes(bf16, K, qcap);
+  if (a.n_ladder > 16)
+    throw std::runtime_error("ladder length > 16 unsupported");
+  const size_t lds = (size_t)kfp_lds_bytes(bf16, a.K, qcap);
   if (qcap <= 0 || qcap > 65535 || lds > 64 * 1024)
     throw std::runtime_error("KFP: qcap exceeds the workgroup LDS budget");
   const int grid = (n_pack + KFP_NODES - 1) / KFP_NODES;
 #define KFP_LAUNCH(BF, SK)                                                  \
   hipLaunchKernelGGL((kfp_sparse_t<BF, SK>), dim3(grid), dim3(WAVE), lds,   \
-                     stream, K, indptr, indices, sumF, order, pos, n_pack,  \
-                     soffset, sidx, sval, scount, epre, bound, goffset,     \
-                     gidx, gval, gcount, llh, GGp, ladder, best, n_ladder,  \
-                     qcap, alpha, min_p, max_p, min_f, max_f)
+                     stream, a.K, a.indptr, a.indices, a.sumF, a.order,     \
+                     pos, n_pack, SWEEP_SHARED(a), qcap, SWEEP_CLAMPS(a))
   if (bf16) {
     if (skip) KFP_LAUNCH(true, true); else KFP_LAUNCH(true, false);
   } else {
@@ -4874,6 +4692,8 @@ extern "C" void launch_kfp(int bf16, const long long* indptr,
 #undef KFP_LAUNCH
   HIP_CHECK(hipGetLastError());
 }
+#undef SWEEP_SHARED
+#undef SWEEP_CLAMPS
 
 extern "C" int k3w_group() { return K3W_G; }
 

@@ -6,6 +6,8 @@
 
 #include <optional>
 
+#include "sparse_sweep.h"
+
 extern "C" void launch_k1(const float*, const long long*, const int*,
                           const float*, const int*, float*, double*, int, int,
                           float, float, hipStream_t);
@@ -63,10 +65,6 @@ extern "C" void launch_k1_chunked(const void*, int, const long long*,
 extern "C" void launch_k6(void*, int, int, const long long*,
                           const long long*, const long long*, int, long long,
                           long long, int, hipStream_t);
-extern "C" void launch_kcs_lists(const void*, int, int, int,
-                                 const long long*, const int*, const float*,
-                                 const int*, const unsigned char*, int,
-                                 float*, hipStream_t);
 extern "C" void launch_k7_count(const void*, int, int, int, int, float, int*,
                                 hipStream_t);
 extern "C" void launch_k7_fill(const void*, int, int, int, int, float,
@@ -385,40 +383,6 @@ void edge_grad_llh_chunked(torch::Tensor F, torch::Tensor indptr,
 }
 
 // Sparse-adaptive sweep (KAF/K1S/K2S/K3S — docs/sparse_sweep_design.md).
-extern "C" void launch_kaf(const void*, int, int, int, int,
-                           const long long*, int*, int*, float*, int,
-                           const unsigned char*, const int*, int,
-                           hipStream_t);
-extern "C" void launch_kfs(const void*, int, const long long*, const int*,
-                           const float*, const int*, int, const long long*,
-                           const int*, const float*, const int*,
-                           const int*, const int*, const long long*, int*,
-                           float*, int*, double*, const float*, const float*,
-                           float*, int, int, int, float, float, float,
-                           float, float, hipStream_t);
-extern "C" void launch_kfw(int, const long long*, const int*, const float*,
-                           const int*, int, const int*, int, const long long*,
-                           const int*, const float*, const int*,
-                           const int*, const int*, const long long*, int*,
-                           float*, int*, double*, const float*, const float*,
-                           float*, int, int, int, float, float, float,
-                           float, float, int, hipStream_t);
-extern "C" long long kfw_lds_bytes(int, int, int);
-extern "C" int k3w_group();
-extern "C" long long kfp_lds_bytes(int, int, int);
-extern "C" void launch_kfp(int, const long long*, const int*, const float*,
-                           const int*, const int*, int, const long long*,
-                           const int*, const float*, const int*,
-                           const int*, const int*, const long long*, int*,
-                           float*, int*, double*, const float*, const float*,
-                           float*, int, int, int, float, float, float,
-                           float, float, int, hipStream_t);
-extern "C" void launch_k3s(void*, int, const int*, int, int,
-                           const long long*, const int*, const float*,
-                           const int*, const float*, const long long*, int*,
-                           float*, int*, unsigned char*, int, int, float,
-                           float, hipStream_t);
-
 // A side stream per device with its fork / join events.  The single
 // (one wave per node) part of a packed wave class holds the widest nodes
 // of the class: a few thousand long waves that fill a fraction of the
@@ -526,6 +490,7 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
   CHECK_IN(GG, torch::kFloat32);
   CHECK_IN(ladder, torch::kFloat32);
   CHECK_IN(best, torch::kFloat32);
+  const int bf16 = is_bf16(F) ? 1 : 0;
   const int n_blocks = (int)order.size(0);
   TORCH_CHECK(goffset.size(0) >= n_blocks && gcount.size(0) >= n_blocks);
   TORCH_CHECK(epre.size(0) == indices.size(0), "epre must be [nnz]");
@@ -545,8 +510,7 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
     TORCH_CHECK(n_pack >= 0 && n_pack <= n_wave, "n_pack out of range");
     TORCH_CHECK(wsplit->dim() == 1 && wsplit->size(0) >= n_wave,
                 "wsplit must hold the wave class");
-    TORCH_CHECK(kfp_lds_bytes(is_bf16(F) ? 1 : 0, (int)F.size(1), (int)qcap) <=
-                    64 * 1024,
+    TORCH_CHECK(kfp_lds_bytes(bf16, (int)F.size(1), (int)qcap) <= 64 * 1024,
                 "qcap exceeds the packed kernel's LDS budget");
     wsp = wsplit->data_ptr<int>();
     if (n_pack > 0 && n_pack < n_wave) {
@@ -562,50 +526,41 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
   }
   const int w_first = packed ? (int)n_pack : (int)n_block;
   const int w_count = packed ? n_wave - (int)n_pack : n_wave;
+  SweepArgs a;
+  a.K = (int)F.size(1);
+  a.indptr = i64p(indptr);
+  a.indices = indices.data_ptr<int>();
+  a.sumF = sumF.data_ptr<float>();
+  a.order = order.data_ptr<int>();
+  a.soffset = i64p(soffset);
+  a.sidx = sidx.data_ptr<int>();
+  a.sval = sval.data_ptr<float>();
+  a.scount = scount.data_ptr<int>();
+  a.epre = epre.data_ptr<int>();
+  a.bound = bound.data_ptr<int>();
+  a.goffset = i64p(goffset);
+  a.gidx = gidx.data_ptr<int>();
+  a.gval = gval.data_ptr<float>();
+  a.gcount = gcount.data_ptr<int>();
+  a.llh = llh.data_ptr<double>();
+  a.GG = GG.data_ptr<float>();
+  a.ladder = ladder.data_ptr<float>();
+  a.best = best.data_ptr<float>();
+  a.n_ladder = (int)ladder.size(0);
+  a.alpha = (float)alpha;
+  a.min_p = (float)min_p;
+  a.max_p = (float)max_p;
+  a.min_f = (float)min_f;
+  a.max_f = (float)max_f;
   if (w_count > 0)
-    launch_kfw(is_bf16(F) ? 1 : 0,
-               reinterpret_cast<const long long*>(indptr.data_ptr<int64_t>()),
-               indices.data_ptr<int>(), sumF.data_ptr<float>(),
-               order.data_ptr<int>(), w_first, wsp, w_count, i64p(soffset),
-               sidx.data_ptr<int>(), sval.data_ptr<float>(),
-               scount.data_ptr<int>(), epre.data_ptr<int>(),
-               bound.data_ptr<int>(), i64p(goffset),
-               gidx.data_ptr<int>(), gval.data_ptr<float>(),
-               gcount.data_ptr<int>(), llh.data_ptr<double>(),
-               GG.data_ptr<float>(), ladder.data_ptr<float>(),
-               best.data_ptr<float>(), (int)ladder.size(0), (int)wcap,
-               (int)F.size(1), (float)alpha, (float)min_p, (float)max_p,
-               (float)min_f, (float)max_f, skip ? 1 : 0, wave_s);
+    launch_kfw(a, bf16, w_first, wsp, w_count, (int)wcap, skip ? 1 : 0,
+               wave_s);
   if (side) TORCH_CHECK(hipEventRecord(side->join, wave_s) == hipSuccess);
   if (packed)
-    launch_kfp(is_bf16(F) ? 1 : 0, i64p(indptr), indices.data_ptr<int>(),
-               sumF.data_ptr<float>(), order.data_ptr<int>(), wsp,
-               (int)n_pack, i64p(soffset), sidx.data_ptr<int>(),
-               sval.data_ptr<float>(), scount.data_ptr<int>(),
-               epre.data_ptr<int>(), bound.data_ptr<int>(), i64p(goffset),
-               gidx.data_ptr<int>(), gval.data_ptr<float>(),
-               gcount.data_ptr<int>(), llh.data_ptr<double>(),
-               GG.data_ptr<float>(), ladder.data_ptr<float>(),
-               best.data_ptr<float>(), (int)ladder.size(0), (int)qcap,
-               (int)F.size(1), (float)alpha, (float)min_p, (float)max_p,
-               (float)min_f, (float)max_f, skip ? 1 : 0, main_s);
+    launch_kfp(a, bf16, wsp, (int)n_pack, (int)qcap, skip ? 1 : 0, main_s);
   if (side)
     TORCH_CHECK(hipStreamWaitEvent(main_s, side->join, 0) == hipSuccess);
-  launch_kfs(F.data_ptr(), is_bf16(F) ? 1 : 0,
-             reinterpret_cast<const long long*>(indptr.data_ptr<int64_t>()),
-             indices.data_ptr<int>(), sumF.data_ptr<float>(),
-             order.data_ptr<int>(), (int)n_block,
-             reinterpret_cast<const long long*>(soffset.data_ptr<int64_t>()),
-             sidx.data_ptr<int>(), sval.data_ptr<float>(),
-             scount.data_ptr<int>(),
-             epre.data_ptr<int>(), bound.data_ptr<int>(),
-             reinterpret_cast<const long long*>(goffset.data_ptr<int64_t>()),
-             gidx.data_ptr<int>(), gval.data_ptr<float>(),
-             gcount.data_ptr<int>(), llh.data_ptr<double>(),
-             GG.data_ptr<float>(), ladder.data_ptr<float>(),
-             best.data_ptr<float>(), (int)ladder.size(0), (int)cap,
-             (int)F.size(1), (float)alpha, (float)min_p, (float)max_p,
-             (float)min_f, (float)max_f, current_stream());
+  launch_kfs(a, F.data_ptr(), bf16, (int)n_block, (int)cap, main_s);
 }
 
 void sparse_commit(torch::Tensor F, torch::Tensor order,
@@ -679,10 +634,7 @@ void seed_init(torch::Tensor F_local, torch::Tensor sindptr,
               ") must equal the length of snbrs (", snbrs.size(0), ")");
   launch_k6(F_local.data_ptr(), is_bf16(F_local) ? 1 : 0,
             (int)F_local.size(1),
-            reinterpret_cast<const long long*>(sindptr.data_ptr<int64_t>()),
-            reinterpret_cast<const long long*>(snbrs.data_ptr<int64_t>()),
-            reinterpret_cast<const long long*>(seeds.data_ptr<int64_t>()),
-            n_seeds, (long long)start, (long long)stop,
+            i64p(sindptr), i64p(snbrs), i64p(seeds), n_seeds, (long long)start, (long long)stop,
             include_seed ? 1 : 0, current_stream());
 }
 
@@ -708,14 +660,6 @@ void sparse_colsum(torch::Tensor F_local, torch::Tensor soffset,
                    dirty.data_ptr<uint8_t>(), (int)cap,
                    partials.data_ptr<float>(), current_stream());
 }
-
-extern "C" void launch_kcs_stage2(const float*, int, int, float*,
-                                  hipStream_t);
-extern "C" int route_tile();
-extern "C" void launch_route(const long long*, const int*, const int*,
-                             const int*, int, int, int, const float*, int,
-                             int*, int*, unsigned char*, int*, int*, int*,
-                             float*, int*, int, int*, int*, hipStream_t);
 
 // Stage 2 of the column-sum refresh: out[k] = sum_s partials[s, k] in a
 // fixed order (see kcs_stage2).

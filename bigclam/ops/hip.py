@@ -272,7 +272,6 @@ def sparse_sweep_part(
     epre: torch.Tensor,
     bound: torch.Tensor,
     goffset: torch.Tensor,
-    gpool_size: int,  # kept for API stability; pools come from the state
     cap: int,
     llh_out: torch.Tensor,
     best_out: torch.Tensor,
