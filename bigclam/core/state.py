@@ -428,8 +428,13 @@ class ShardState:
         buffers so a carried pack's ``order``/``order_d`` stay valid
         until that pack is committed and read.  With ``qcap > 0`` the
         same pass splits the wave class for the packed kernel and leaves
-        ``(wsplit, n_pack)`` in ``self._wave_split`` (read by this sweep's
-        fused launch only, so one buffer serves)."""
+        ``(wsplit, n_pack, n_zero, n_rep, zscr)`` in ``self._wave_split``
+        (read by this sweep's fused launch only, so one buffer serves):
+        ``wsplit[:n_pack + n_zero]`` the packed nodes,
+        ``wsplit[n_pack + n_zero:]`` the single-wave part; ``zscr`` lists
+        the packed ones again as [``n_pack`` with bound > 0 | ``n_zero``
+        with bound 0, the zero class (``sparse_zero``; empty when off)]
+        and holds the zero class's ``n_rep`` representatives."""
         ext = _hip_ops().ensure_loaded()
         rt = self._rt
         if rt is None:
@@ -448,16 +453,25 @@ class ShardState:
                 "by_class": [torch.empty(n, **i32) for _ in range(2)],
                 "wsplit": torch.empty(n, **i32),
                 "pscr": torch.empty(4 * (nt3 // 3) + 1, **i32),
+                "zscr": torch.empty(
+                    int(ext.sparse_zero_layout()[2]) + 6 * (nt3 // 3) + n,
+                    **i32,
+                ),
             }
         self._rt_flip ^= 1
         by_class = rt["by_class"][self._rt_flip]
-        split = (qcap, rt["wsplit"], rt["pscr"]) if qcap > 0 else ()
-        n_blk, n_wave, _, *n_pack = ext.sparse_route(
+        split = (
+            (qcap, rt["wsplit"], rt["pscr"], rt["zscr"], self.sparse_zero)
+            if qcap > 0 else ()
+        )
+        n_blk, n_wave, _, *counts = ext.sparse_route(
             self.indptr, self.indices, scount, self.order, self.sumF,
             cap, wcap, rt["epre"], rt["bound"], rt["cls"], rt["tcount"],
             rt["tbase"], rt["totals"], rt["GG"], by_class, *split,
         )  # <- the one host sync
-        self._wave_split = (rt["wsplit"], n_pack[0]) if n_pack else None
+        self._wave_split = (
+            (rt["wsplit"], *counts, rt["zscr"]) if counts else None
+        )
         return rt["epre"], rt["bound"], by_class, rt["GG"], n_blk, \
             n_blk + n_wave
 
@@ -575,6 +589,18 @@ class ShardState:
         BIGCLAM_SPARSE_SKIP=0 selects the builds without it, the A/B
         reference of the tests and the benchmark."""
         return os.environ.get("BIGCLAM_SPARSE_SKIP", "1") != "0"
+
+    @property
+    def sparse_zero(self) -> bool:
+        """Route the packed nodes with bound 0 to the zero class: the
+        sweep computes one representative per degree and copies its llh
+        and step to the others (``kz_fill``) instead of running each
+        through KFP.  Every output is bitwise the same;
+        BIGCLAM_SPARSE_ZERO=0 keeps them in KFP, the A/B reference.  Off
+        whenever the packed kernel is (``sparse_qcap == 0``)."""
+        if self.sparse_qcap <= 0:
+            return False
+        return os.environ.get("BIGCLAM_SPARSE_ZERO", "1") != "0"
 
     @property
     def sparse_allowed(self) -> bool:
@@ -768,7 +794,9 @@ class ShardState:
             epre, bound32, by_class, GG, n_blk, n_s = self._route_torch(
                 scount, cap, wcap
             )
-        wsplit, n_pack = self._wave_split or (None, 0)
+        wsplit, n_pack, n_zero, n_rep, zscr = self._wave_split or (
+            None, 0, 0, 0, None
+        )
         order_s = by_class[:n_s]
         # engage only when a real fraction of nodes routes: at low K /
         # moderate density the bound exceeds cap for most nodes and the
@@ -824,10 +852,14 @@ class ShardState:
             n_block=n_blk, wcap=wcap, GG=GG,
             qcap=qcap if wsplit is not None else 0, wsplit=wsplit,
             n_pack=n_pack, skip=self.sparse_skip,
+            n_zero=n_zero, n_rep=n_rep, zscr=zscr,
         )
         pack["n_block"] = n_blk  # order[:n_block] block class, rest wave
         pack["wcap"] = wcap
-        pack["n_pack"] = n_pack  # wave-class nodes run four per wave
+        # wave-class nodes on the packed path (the front of wsplit), and
+        # how many of them are zero-class nodes filled from a representative
+        pack["n_pack"] = n_pack + n_zero
+        pack["n_zero"] = n_zero
         if n_d:
             torch.cuda.current_stream(dev).wait_stream(self._side_stream)
         pack["best"] = best

@@ -2565,6 +2565,16 @@ __global__ void __launch_bounds__(BLOCK) kaf_support_t(
 // non-negative ints stay associative, so bound == min(true, cap + 1) and
 // epre is exact on every node with bound <= cap — the only readers.  A
 // node stops walking once it saturates (it is dense; its epre is unread).
+//
+// The zero class (zscr given, sparse_sweep.h's ZR_* layout): a packable
+// node with bound 0 has no support of its own and only empty edges, so
+// what the sweep writes for it depends on its degree alone.  The same
+// three launches list the packed part of wsplit once more, as [bound > 0 |
+// zero] (zsplit, at the end of zscr; wsplit itself does not change), both
+// in launch order, and name the first zero node of every degree (the
+// launch order is degree-descending, so each degree is one run) as that
+// degree's representative: the sweep computes the representatives and
+// copies their outputs to the rest (kz_fill).
 
 #define RT_TILE 64     // launch-order positions per tile (one wave places it)
 #define RT_GRP 16      // lanes per node in the bounds walk
@@ -2584,7 +2594,8 @@ __global__ void __launch_bounds__(BLOCK) kr_bounds(
     const int* __restrict__ scount, const int* __restrict__ order,
     int n_local, int cap, int wcap, int* __restrict__ epre,
     int* __restrict__ bound, unsigned char* __restrict__ cls,
-    int* __restrict__ tcount, int qcap, int* __restrict__ pscr) {
+    int* __restrict__ tcount, int qcap, int* __restrict__ pscr,
+    int* __restrict__ zscr, int zero) {
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   const int wid = tid >> 6;
@@ -2597,8 +2608,10 @@ __global__ void __launch_bounds__(BLOCK) kr_bounds(
   __shared__ int s_nhub;
   __shared__ int s_scan[NWAVE];
   __shared__ unsigned char s_el[RT_TILE];  // packable (KFP) wave-class node
-  if (tid == 0) s_nhub = 0;
-  if (tid < RT_TILE) s_el[tid] = 0;
+  __shared__ unsigned char s_z[RT_TILE];   // zero class: degree + 1, else 0
+  __shared__ u32 s_dm;  // degrees of the tile's zero-class nodes, one bit each
+  if (tid == 0) s_nhub = 0, s_dm = 0u;
+  if (tid < RT_TILE) s_el[tid] = 0, s_z[tid] = 0;
   __syncthreads();
   constexpr int NGRP = BLOCK / RT_GRP;
   for (int r = 0; r < RT_TILE / NGRP; ++r) {
@@ -2632,8 +2645,13 @@ __global__ void __launch_bounds__(BLOCK) kr_bounds(
       bound[u] = b;
       const int c = route_class(b, cap, wcap);
       s_cls[q] = (unsigned char)c;
-      s_el[q] = (unsigned char)(c == 1 && qcap > 0 && b <= qcap &&
-                                deg <= KFP_DEG);  // qcap 0: nothing packs
+      const bool el = c == 1 && qcap > 0 && b <= qcap &&
+                      deg <= KFP_DEG;  // qcap 0: nothing packs
+      s_el[q] = (unsigned char)el;
+      if (zero && el && b == 0) {
+        s_z[q] = (unsigned char)(deg + 1);
+        atomicOr(&s_dm, 1u << deg);
+      }
     }
   }
   __syncthreads();
@@ -2689,7 +2707,9 @@ __global__ void __launch_bounds__(BLOCK) kr_bounds(
   if (wid == 0) {  // RT_TILE == WAVE: one lane per position
     const int p = p0 + lane;
     const int c = p < n_local ? (int)s_cls[lane] : 3;
-    if (p < n_local) cls[p] = (unsigned char)c;
+    // a zero-class position carries its degree + 1 above the class bits
+    const int zd = p < n_local ? (int)s_z[lane] : 0;
+    if (p < n_local) cls[p] = (unsigned char)(c | (zd << 2));
     const unsigned long long m0 = __ballot(c == 0);
     const unsigned long long m1 = __ballot(c == 1);
     const unsigned long long m2 = __ballot(c == 2);
@@ -2698,10 +2718,15 @@ __global__ void __launch_bounds__(BLOCK) kr_bounds(
           __popcll(lane == 0 ? m0 : (lane == 1 ? m1 : m2));
     if (pscr) {  // the packed / single split of the wave class
       const unsigned long long me = __ballot(p < n_local && s_el[lane]);
+      const unsigned long long mz = __ballot(zd != 0);
       if (lane == 0) {
         pscr[blockIdx.x * 3] = __popcll(me);
         pscr[blockIdx.x * 3 + 1] = (int)(unsigned)(me & 0xffffffffull);
         pscr[blockIdx.x * 3 + 2] = (int)(unsigned)(me >> 32);
+        // the scan's record with zscr: packable, zero class, its degrees
+        if (zscr)
+          *reinterpret_cast<int4*>(zscr + ZR_TILES + blockIdx.x * 4) =
+              make_int4(__popcll(me), __popcll(mz), (int)s_dm, 0);
       }
     }
   }
@@ -2712,7 +2737,7 @@ __global__ void __launch_bounds__(RT_SCAN) kr_scan(
     const int* __restrict__ tcount, int n_tiles, int* __restrict__ tbase,
     int* __restrict__ totals, const float* __restrict__ sumF, int K,
     float* __restrict__ GG, const int* __restrict__ pcnt,
-    int* __restrict__ pbase) {
+    int* __restrict__ pbase, int* __restrict__ zscr) {
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   const int wid = tid >> 6;
@@ -2720,6 +2745,17 @@ __global__ void __launch_bounds__(RT_SCAN) kr_scan(
   __shared__ int s_w[NW][3];
   __shared__ float s_g[NW];
   __shared__ int s_p[NW];
+  __shared__ int s_z[NW];
+  __shared__ u32 s_d[NW];
+  // zero class (zscr, with pcnt): per tile one 16-byte record (packable
+  // count, zero count, degree mask) in, zero base + the degrees of the
+  // earlier tiles out
+  const int4* zt =
+      zscr ? reinterpret_cast<const int4*>(zscr + ZR_TILES) : nullptr;
+  int2* zb =
+      zscr ? reinterpret_cast<int2*>(zscr + ZR_TILES + 4 * n_tiles) : nullptr;
+  int cz = 0;
+  u32 cd = 0u;
   const int chunk = (n_tiles + RT_SCAN - 1) / RT_SCAN;
   const int t0 = min(tid * chunk, n_tiles);
   const int t1 = min(t0 + chunk, n_tiles);
@@ -2731,10 +2767,19 @@ __global__ void __launch_bounds__(RT_SCAN) kr_scan(
     c[0] += tcount[t * 3];
     c[1] += tcount[t * 3 + 1];
     c[2] += tcount[t * 3 + 2];
-    if (pcnt) cp += pcnt[t * 3];
+    if (zt) {
+      const int4 r = zt[t];
+      cp += r.x;
+      cz += r.y;
+      cd |= (u32)r.z;
+    } else if (pcnt) {
+      cp += pcnt[t * 3];
+    }
   }
   int incl[3] = {c[0], c[1], c[2]};
   int inclp = cp;
+  int inclz = cz;
+  u32 incld = cd;
 #pragma unroll
   for (int off = 1; off < WAVE; off <<= 1) {
 #pragma unroll
@@ -2744,6 +2789,10 @@ __global__ void __launch_bounds__(RT_SCAN) kr_scan(
     }
     const int vp = __shfl_up(inclp, off, WAVE);
     if (lane >= off) inclp += vp;
+    const int vz = __shfl_up(inclz, off, WAVE);
+    if (lane >= off) inclz += vz;
+    const u32 vd = __shfl_up(incld, off, WAVE);
+    if (lane >= off) incld |= vd;
   }
   // GG in a fixed order: strided per-thread sums, xor tree, waves in order
   float g = 0.f;
@@ -2756,7 +2805,12 @@ __global__ void __launch_bounds__(RT_SCAN) kr_scan(
     s_w[wid][2] = incl[2];
     s_g[wid] = g;
     s_p[wid] = inclp;
+    s_z[wid] = inclz;
+    s_d[wid] = incld;
   }
+  // degrees before this thread's chunk, inside its wave
+  u32 rund = __shfl_up(incld, 1, WAVE);
+  if (lane == 0) rund = 0u;
   __syncthreads();
   int run[3];
 #pragma unroll
@@ -2766,19 +2820,44 @@ __global__ void __launch_bounds__(RT_SCAN) kr_scan(
     run[j] = b + incl[j] - c[j];
   }
   int runp = inclp - cp;
-  for (int wv = 0; wv < wid; ++wv) runp += s_p[wv];
+  int runz = inclz - cz;
+  for (int wv = 0; wv < wid; ++wv) {
+    runp += s_p[wv];
+    runz += s_z[wv];
+    rund |= s_d[wv];
+  }
   for (int t = t0; t < t1; ++t) {
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       tbase[t * 3 + j] = run[j];
       run[j] += tcount[t * 3 + j];
     }
-    if (pcnt) {
+    if (zt) {
+      const int4 r = zt[t];
+      pbase[t] = runp;
+      zb[t] = make_int2(runz, (int)rund);
+      runp += r.x;
+      runz += r.y;
+      rund |= (u32)r.z;
+    } else if (pcnt) {
       pbase[t] = runp;
       runp += pcnt[t * 3];
     }
   }
-  if (pcnt && tid == RT_SCAN - 1) pbase[n_tiles] = runp;
+  if (pcnt && tid == RT_SCAN - 1) {
+    pbase[n_tiles] = runp;
+    if (zscr) {  // the last thread's running values are the totals
+      zscr[ZR_NPACK] = runp - runz;
+      zscr[ZR_NZERO] = runz;
+      zscr[ZR_NREP] = __popc(rund);
+      zscr[ZR_MASK] = (int)rund;
+    }
+  }
+  if (zscr && tid <= KFP_DEG) {
+    // no representative yet; kr_place fills the degrees that have one
+    zscr[ZR_REP + tid] = -1;
+    zscr[ZR_NODE + tid] = -1;
+  }
   if (tid == 0) {
     float gs = 0.f;
     int tot[3] = {0, 0, 0};
@@ -2792,6 +2871,7 @@ __global__ void __launch_bounds__(RT_SCAN) kr_scan(
     totals[0] = tot[0];
     totals[1] = tot[1];
     totals[2] = tot[2];
+    if (zscr) zscr[0] = tot[0], zscr[1] = tot[1], zscr[2] = tot[2];
   }
 }
 
@@ -2801,12 +2881,19 @@ __global__ void __launch_bounds__(BLOCK) kr_place(
     const int* __restrict__ tbase, const int* __restrict__ totals,
     int n_local, int n_tiles, int* __restrict__ by_class,
     const int* __restrict__ pcnt, const int* __restrict__ pbase,
-    int* __restrict__ wsplit) {
+    int* __restrict__ wsplit, int* __restrict__ zscr) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int tile = blockIdx.x * NWAVE + (threadIdx.x >> 6);
   if (tile >= n_tiles) return;  // wave-uniform
   const int p = tile * RT_TILE + lane;
-  const int c = p < n_local ? (int)cls[p] : 3;
+  const int cz = p < n_local ? (int)cls[p] : 3;
+  const int c = cz & 3;
+  // zero class: kr_bounds left degree + 1 above the class bits; the tile's
+  // ballot (wave-uniform), the zero lanes below this one
+  const bool z = (cz >> 2) != 0;
+  const unsigned long long zm = __ballot(z);
+  const unsigned long long zbelow = zm & ((1ull << lane) - 1ull);
+  int zpos = 0, node = 0;  // a zero node's pack position and id
   const unsigned long long m0 = __ballot(c == 0);
   const unsigned long long m1 = __ballot(c == 1);
   const unsigned long long m2 = __ballot(c == 2);
@@ -2815,7 +2902,7 @@ __global__ void __launch_bounds__(BLOCK) kr_place(
     const int rank = __popcll(m & ((1ull << lane) - 1ull));
     const int cbase =
         (c >= 1 ? totals[0] : 0) + (c == 2 ? totals[1] : 0);
-    by_class[cbase + tbase[tile * 3 + c] + rank] = order[p];
+    by_class[cbase + tbase[tile * 3 + c] + rank] = node = order[p];
     if (wsplit && c == 1) {
       // stable two-way partition of the wave class: packable nodes'
       // pack positions first, the others after, both in launch order
@@ -2824,9 +2911,33 @@ __global__ void __launch_bounds__(BLOCK) kr_place(
           ((unsigned long long)(unsigned)pcnt[tile * 3 + 2] << 32) |
           (unsigned long long)(unsigned)pcnt[tile * 3 + 1];
       const int eb = pbase[tile] + __popcll(em & ((1ull << lane) - 1ull));
-      const int slot =
-          ((em >> lane) & 1ull) ? eb : pbase[n_tiles] + (wrank - eb);
-      wsplit[slot] = totals[0] + wrank;
+      const bool el = (em >> lane) & 1ull;
+      const int slot = el ? eb : pbase[n_tiles] + (wrank - eb);
+      wsplit[slot] = zpos = totals[0] + wrank;
+      if (zscr && el) {
+        // the packed part again in its own list (zsplit), stable: bound
+        // > 0 first, the zero class after; zr = zero nodes before this one
+        const int zr =
+            zscr[ZR_TILES + 4 * n_tiles + tile * 2] + __popcll(zbelow);
+        zscr[ZR_TILES + 6 * n_tiles + (z ? zscr[ZR_NPACK] + zr : eb - zr)] =
+            zpos;
+      }
+    }
+  }
+  if (zm) {  // wave-uniform
+    // representatives: the first zero node of each degree — no zero lane
+    // of that degree below it, none in an earlier tile
+    const int d = (cz >> 2) - 1;  // -1: not a zero node
+    unsigned long long same = 0ull;
+    for (int dd = 0; dd <= KFP_DEG; ++dd) {
+      const unsigned long long md = __ballot(d == dd);
+      if (d == dd) same = md;
+    }
+    const u32 seen = (u32)zscr[ZR_TILES + 4 * n_tiles + tile * 2 + 1];
+    if (z && !(same & zbelow) && !((seen >> d) & 1u)) {
+      const u32 all = (u32)zscr[ZR_MASK];
+      zscr[ZR_REP + __popc(all >> (d + 1))] = zpos;  // degree-descending
+      zscr[ZR_NODE + d] = node;
     }
   }
 }
@@ -3772,6 +3883,34 @@ __global__ void __launch_bounds__(WAVE) kfp_sparse_t(
   if (gl == 0 && alive) best[u] = pick;
 }
 
+// kz_fill: the zero class (routing, above).  A packable node with bound 0
+// has su = total = ns = 0 in KFP: llh_acc is the fixed 16-lane tree over
+// deg copies of the empty edge's term, fs = ff = gg = 0, every trial is the
+// four-accumulator chain of deg copies of c0, and gg = GG[0] — functions
+// of deg, GG, the ladder, alpha and the clamps, equal for every such node
+// of one sweep.  KFP has run one representative per degree (zrep_node,
+// -1: no such node); the others take its llh and best, bit for bit, and
+// an empty gradient list.  One thread per position of the zero segment
+// pos[0 .. n_zero); a representative is never written here, so the reads
+// race with nothing.
+__global__ void __launch_bounds__(BLOCK) kz_fill(
+    const long long* __restrict__ indptr, const int* __restrict__ order,
+    const int* __restrict__ pos, int n_zero,
+    const int* __restrict__ zrep_node, int* __restrict__ gcount,
+    double* __restrict__ llh, float* __restrict__ best) {
+  const int i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= n_zero) return;
+  const int b = pos[i];
+  const int u = order[b];
+  const long long deg = indptr[u + 1] - indptr[u];
+  if (deg < 0 || deg > KFP_DEG) return;  // routing sends none such
+  const int r = zrep_node[deg];
+  if (r < 0 || r == u) return;
+  llh[u] = llh[r];
+  best[u] = best[r];
+  gcount[b] = 0;
+}
+
 // K3S also REWRITES the committed row's persistent support list
 // (sidx/sval/scount) so the next sweep's KAF only rescans rows the
 // DENSE path committed: the new row's support is a subset of S_u, and
@@ -4692,6 +4831,16 @@ extern "C" void launch_kfp(const SweepArgs& a, int bf16, const int* pos,
 #undef KFP_LAUNCH
   HIP_CHECK(hipGetLastError());
 }
+
+// after the KFP launch that ran the representatives, on its stream
+extern "C" void launch_kz_fill(const SweepArgs& a, const int* pos, int n_zero,
+                               const int* zrep_node, hipStream_t stream) {
+  if (n_zero == 0) return;
+  hipLaunchKernelGGL(kz_fill, dim3((n_zero + BLOCK - 1) / BLOCK), dim3(BLOCK),
+                     0, stream, a.indptr, a.order, pos, n_zero, zrep_node,
+                     a.gcount, a.llh, a.best);
+  HIP_CHECK(hipGetLastError());
+}
 #undef SWEEP_SHARED
 #undef SWEEP_CLAMPS
 
@@ -4791,30 +4940,33 @@ extern "C" int route_tile() { return RT_TILE; }
 // host read.  tcount/tbase hold 3 ints per tile.  pscr (nullable, with
 // wsplit): [3 ints per tile: packable count, ballot lo, hi | a base per
 // tile | n_pack] = 4 * tiles + 1 ints, for the packed / single split of
-// the wave class.
+// the wave class.  zscr (nullable, with pscr; ZR_* in sparse_sweep.h):
+// the five counts side by side, the zero class's representatives, and its
+// per-tile scratch and, after it, zsplit [n_local]; `zero` = 0 keeps the zero
+// class empty.
 extern "C" void launch_route(const long long* indptr, const int* indices,
                              const int* scount, const int* order,
                              int n_local, int cap, int wcap,
                              const float* sumF, int K, int* epre, int* bound,
                              unsigned char* cls, int* tcount, int* tbase,
                              int* totals, float* GG, int* by_class,
-                             int qcap, int* pscr, int* wsplit,
-                             hipStream_t stream) {
+                             int qcap, int* pscr, int* wsplit, int* zscr,
+                             int zero, hipStream_t stream) {
   static_assert(RT_TILE == WAVE && RT_TILE % (BLOCK / RT_GRP) == 0,
                 "one wave places a tile; groups cover it in whole rounds");
   const int n_tiles = (n_local + RT_TILE - 1) / RT_TILE;
   if (n_tiles > 0)
     hipLaunchKernelGGL(kr_bounds, dim3(n_tiles), dim3(BLOCK), 0, stream,
                        indptr, indices, scount, order, n_local, cap, wcap,
-                       epre, bound, cls, tcount, qcap, pscr);
+                       epre, bound, cls, tcount, qcap, pscr, zscr, zero);
   hipLaunchKernelGGL(kr_scan, dim3(1), dim3(RT_SCAN), 0, stream, tcount,
                      n_tiles, tbase, totals, sumF, K, GG, pscr,
-                     pscr ? pscr + 3 * n_tiles : nullptr);
+                     pscr ? pscr + 3 * n_tiles : nullptr, zscr);
   if (n_tiles > 0)
     hipLaunchKernelGGL(kr_place, dim3((n_tiles + NWAVE - 1) / NWAVE),
                        dim3(BLOCK), 0, stream, order, cls, tbase, totals,
                        n_local, n_tiles, by_class, pscr,
-                       pscr ? pscr + 3 * n_tiles : nullptr, wsplit);
+                       pscr ? pscr + 3 * n_tiles : nullptr, wsplit, zscr);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -462,7 +462,8 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
                   double min_p, double max_p, double min_f, double max_f,
                   int64_t n_block, int64_t wcap, int64_t qcap,
                   std::optional<torch::Tensor> wsplit, int64_t n_pack,
-                  bool skip) {
+                  bool skip, int64_t n_zero, int64_t n_rep,
+                  std::optional<torch::Tensor> zscr) {
   // order[:n_block] runs the block kernel (KFS), order[n_block:] the
   // one-wave-per-node kernel (KFW, bound <= wcap); pools and gcount are
   // indexed by position in `order` for both.  With qcap > 0 and the
@@ -471,6 +472,12 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
   // wsplit[n_pack:n_wave] one wave per node (KFW).  skip selects the
   // KFW/KFP instantiations that pass over empty edges and empty active
   // sets (bitwise the same outputs; false = the A/B reference).
+  // With zscr (the routing's zero class) the packed part of wsplit holds
+  // n_pack + n_zero positions and zscr lists them again as zsplit = [bound
+  // > 0 | zero]: KFP runs zsplit[:n_pack] and, in a second launch, the n_rep
+  // representatives; kz_fill then copies each degree's llh / best to the
+  // other zero nodes zsplit[n_pack : n_pack + n_zero].  The single part is
+  // wsplit[n_pack + n_zero : n_wave] as without it.
   CHECK_F(F);
   CHECK_IN(indptr, torch::kInt64);
   CHECK_IN(indices, torch::kInt32);
@@ -501,6 +508,10 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
               "wave class needs 0 < wcap <= cap");
   const bool packed = qcap > 0 && wsplit.has_value();
   const int* wsp = nullptr;
+  const int* zsp = nullptr;
+  const int* kfp_pos = nullptr;  // KFP's position list
+  int n_pz = 0;  // packed and zero nodes: the front of wsplit
+  TORCH_CHECK(packed || n_zero == 0, "the zero class needs the packed split");
   hipStream_t main_s = current_stream();
   hipStream_t wave_s = main_s;  // where the single-wave launch goes
   WaveSide* side = nullptr;
@@ -512,8 +523,24 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
                 "wsplit must hold the wave class");
     TORCH_CHECK(kfp_lds_bytes(bf16, (int)F.size(1), (int)qcap) <= 64 * 1024,
                 "qcap exceeds the packed kernel's LDS budget");
-    wsp = wsplit->data_ptr<int>();
-    if (n_pack > 0 && n_pack < n_wave) {
+    wsp = kfp_pos = wsplit->data_ptr<int>();
+    TORCH_CHECK(n_zero >= 0 && n_pack + n_zero <= n_wave,
+                "n_zero out of range");
+    if (n_zero > 0) {
+      TORCH_CHECK(zscr.has_value(), "the zero class needs zscr");
+      CHECK_IN((*zscr), torch::kInt32);
+      const int64_t n_local = bound.size(0);
+      const int64_t zs_at =
+          ZR_TILES + 6 * ((n_local + route_tile() - 1) / route_tile());
+      TORCH_CHECK(zscr->dim() == 1 && zscr->size(0) >= zs_at + n_local,
+                  "zscr must be the routing's buffer");
+      TORCH_CHECK(n_rep > 0 && n_rep <= KFP_DEG + 1 && n_rep <= n_zero,
+                  "n_rep out of range");
+      zsp = zscr->data_ptr<int>();
+      kfp_pos = zsp + zs_at;  // [bound > 0 | zero]
+    }
+    n_pz = (int)(n_pack + n_zero);
+    if (n_pz > 0 && n_pz < n_wave) {
       // both parts non-empty: the single part forks to the side stream
       // (it only reads what the main stream has finished writing, and
       // writes positions no other launch of this call touches)
@@ -524,8 +551,8 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
       wave_s = side->stream;
     }
   }
-  const int w_first = packed ? (int)n_pack : (int)n_block;
-  const int w_count = packed ? n_wave - (int)n_pack : n_wave;
+  const int w_first = packed ? n_pz : (int)n_block;
+  const int w_count = packed ? n_wave - n_pz : n_wave;
   SweepArgs a;
   a.K = (int)F.size(1);
   a.indptr = i64p(indptr);
@@ -557,7 +584,13 @@ void sparse_fused(torch::Tensor F, torch::Tensor indptr,
                wave_s);
   if (side) TORCH_CHECK(hipEventRecord(side->join, wave_s) == hipSuccess);
   if (packed)
-    launch_kfp(a, bf16, wsp, (int)n_pack, (int)qcap, skip ? 1 : 0, main_s);
+    launch_kfp(a, bf16, kfp_pos, (int)n_pack, (int)qcap, skip ? 1 : 0,
+               main_s);
+  if (zsp) {
+    launch_kfp(a, bf16, zsp + ZR_REP, (int)n_rep, (int)qcap, skip ? 1 : 0,
+               main_s);
+    launch_kz_fill(a, kfp_pos + n_pack, (int)n_zero, zsp + ZR_NODE, main_s);
+  }
   if (side)
     TORCH_CHECK(hipStreamWaitEvent(main_s, side->join, 0) == hipSuccess);
   launch_kfs(a, F.data_ptr(), bf16, (int)n_block, (int)cap, main_s);
@@ -684,6 +717,16 @@ void colsum_stage2(torch::Tensor partials, torch::Tensor out) {
 // the nodes with bound <= qcap and degree <= 16, wsplit[n_pack:n_wave]
 // those of the others, both in launch order; n_pack is returned as a
 // fourth value from the same host sync.  Nothing else changes.
+// With zscr [ZR_TILES + 6 * tiles + n_local] given as well, all counts come
+// back in ONE device-to-host copy (they sit side by side at its start), and
+// with `zero` the packed part is listed once more at the end of zscr
+// (zsplit, from ZR_TILES + 6 * tiles): zsplit[:n_pack] the packable nodes
+// with bound > 0, zsplit[n_pack : n_pack + n_zero] those with bound 0 (the
+// zero class), both in launch order.  wsplit is what it is without zscr: the
+// packed part holds n_pack + n_zero positions.  zscr[ZR_REP ..] then lists the pack position of the first zero
+// node of each degree (degree-descending, -1 past the count), zscr[ZR_NODE
+// + deg] its node id (-1: none).  Returns six values: the three class
+// sizes, n_pack, n_zero and the number of representatives.
 std::vector<int64_t> sparse_route(
     torch::Tensor indptr, torch::Tensor indices, torch::Tensor scount,
     torch::Tensor order, torch::Tensor sumF, int64_t cap, int64_t wcap,
@@ -691,7 +734,8 @@ std::vector<int64_t> sparse_route(
     torch::Tensor tcount, torch::Tensor tbase, torch::Tensor totals,
     torch::Tensor GG, torch::Tensor by_class,
     std::optional<int64_t> qcap, std::optional<torch::Tensor> wsplit,
-    std::optional<torch::Tensor> pscr) {
+    std::optional<torch::Tensor> pscr, std::optional<torch::Tensor> zscr,
+    bool zero) {
   CHECK_IN(indptr, torch::kInt64);
   CHECK_IN(indices, torch::kInt32);
   CHECK_IN(scount, torch::kInt32);
@@ -733,6 +777,18 @@ std::vector<int64_t> sparse_route(
     wsp = wsplit->data_ptr<int>();
     psp = pscr->data_ptr<int>();
   }
+  int* zsp = nullptr;
+  if (zscr.has_value()) {
+    TORCH_CHECK(split, "zscr goes with qcap, wsplit and pscr");
+    CHECK_IN((*zscr), torch::kInt32);
+    TORCH_CHECK(zscr->dim() == 1 &&
+                    zscr->size(0) >= ZR_TILES + 6 * n_tiles + n_local,
+                "zscr must hold ZR_TILES + 6 ints per routing tile + n_local");
+    zsp = zscr->data_ptr<int>();
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(zsp) % 16 == 0,
+                "zscr must be 16-byte aligned");
+  }
+  TORCH_CHECK(!zero || zsp, "the zero class needs zscr");
   hipStream_t stream = current_stream();
   launch_route(i64p(indptr), indices.data_ptr<int>(), scount.data_ptr<int>(),
                order.data_ptr<int>(), (int)n_local, (int)cap, (int)wcap,
@@ -741,7 +797,14 @@ std::vector<int64_t> sparse_route(
                cls.data_ptr<uint8_t>(), tcount.data_ptr<int>(),
                tbase.data_ptr<int>(), totals.data_ptr<int>(),
                GG.data_ptr<float>(), by_class.data_ptr<int>(), q, psp, wsp,
-               stream);
+               zsp, zero ? 1 : 0, stream);
+  if (zsp) {  // every count in one copy
+    int z[ZR_HOST];
+    TORCH_CHECK(hipMemcpyAsync(z, zsp, sizeof(z), hipMemcpyDeviceToHost,
+                               stream) == hipSuccess);
+    TORCH_CHECK(hipStreamSynchronize(stream) == hipSuccess);
+    return {z[0], z[1], z[2], z[ZR_NPACK], z[ZR_NZERO], z[ZR_NREP]};
+  }
   int h[4] = {0, 0, 0, 0};
   TORCH_CHECK(hipMemcpyAsync(h, totals.data_ptr<int>(), 3 * sizeof(int),
                              hipMemcpyDeviceToHost, stream) == hipSuccess);
@@ -933,7 +996,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "KFS/KFW/KFP: fused compact gradient + 16-candidate Armijo for routed "
         "nodes (LDS bitmap active sets); order[:n_block] one block per "
         "node, order[n_block:] one wave per node, or four per wave for the "
-        "pack positions wsplit[:n_pack] when qcap > 0",
+        "pack positions wsplit[:n_pack] when qcap > 0; with zscr the zero "
+        "class among them is filled from its representatives",
         py::arg("F"), py::arg("indptr"), py::arg("indices"), py::arg("sumF"),
         py::arg("order"), py::arg("soffset"), py::arg("sidx"),
         py::arg("sval"), py::arg("scount"), py::arg("epre"),
@@ -943,7 +1007,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("min_p"), py::arg("max_p"), py::arg("min_f"),
         py::arg("max_f"), py::arg("n_block"), py::arg("wcap"),
         py::arg("qcap") = 0, py::arg("wsplit") = py::none(),
-        py::arg("n_pack") = 0, py::arg("skip") = true);
+        py::arg("n_pack") = 0, py::arg("skip") = true,
+        py::arg("n_zero") = 0, py::arg("n_rep") = 0,
+        py::arg("zscr") = py::none());
   m.def("sparse_commit_group", []() { return (int64_t)k3w_group(); },
         "wave-class positions one wave of the sparse commit (K3W) serves");
   m.def("sparse_pack_lds_bytes",
@@ -963,13 +1029,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sparse_route", &sparse_route,
         "routing: node-local support prefix, bounds, classes and the stable "
         "[block | wave | dense] order; returns the three class sizes (and "
-        "n_pack when the packed split is requested)",
+        "n_pack when the packed split is requested; with zscr: n_pack, "
+        "n_zero and the number of zero-class representatives)",
         py::arg("indptr"), py::arg("indices"), py::arg("scount"),
         py::arg("order"), py::arg("sumF"), py::arg("cap"), py::arg("wcap"),
         py::arg("epre"), py::arg("bound"), py::arg("cls"), py::arg("tcount"),
         py::arg("tbase"), py::arg("totals"), py::arg("GG"),
         py::arg("by_class"), py::arg("qcap") = py::none(),
-        py::arg("wsplit") = py::none(), py::arg("pscr") = py::none());
+        py::arg("wsplit") = py::none(), py::arg("pscr") = py::none(),
+        py::arg("zscr") = py::none(), py::arg("zero") = false);
+  m.def("sparse_zero_layout",
+        []() {
+          return std::vector<int64_t>{ZR_REP, ZR_NODE, ZR_TILES};
+        },
+        "zscr offsets: representatives' pack positions, representative node "
+        "by degree, start of the per-tile scratch (6 ints per tile; zsplit "
+        "[n_local] follows it)");
   m.def("sparse_route_tile", []() { return (int64_t)route_tile(); },
         "launch-order positions per routing tile");
   m.def("sparse_commit", &sparse_commit,

@@ -16,6 +16,24 @@
 #define KFP_DEG 16    // most edges of a node on the packed wave path (KFP)
 #define KFP_NODES 4   // nodes per wave in KFP
 
+// Routing's zero-class buffer (int32, ZR_TILES + 6 per routing tile +
+// n_local): the counts the host reads in one copy, the representatives, tile
+// scratch, and zsplit: the packed positions as [bound > 0 | zero class].
+#define ZR_NPACK 3    // [0..2] block / wave / dense; packed with bound > 0
+#define ZR_NZERO 4    // packed with bound 0 (the zero class)
+#define ZR_NREP 5     // representatives = degrees present in the zero class
+#define ZR_HOST 6     // the host's one copy: the ints up to here
+#define ZR_MASK 6     // bit d: a zero node of degree d exists
+#define ZR_REP 8      // [KFP_DEG + 1] pack positions, degree-descending, -1
+#define ZR_NODE 25    // [KFP_DEG + 1] representative node by degree, -1
+#define ZR_TILES 44   // per tile (16 bytes): packable count, zero count, the
+                      // zero nodes' degree mask, 0; then per tile: zero
+                      // base, degrees of the earlier tiles; then zsplit
+                      // [n_local]
+static_assert(ZR_NODE == ZR_REP + KFP_DEG + 1 &&
+                  ZR_TILES >= ZR_NODE + KFP_DEG + 1 && ZR_TILES % 4 == 0,
+              "zero-class buffer layout");
+
 // What KFS, KFW and KFP share (pools by position in `order`, lists by row)
 struct SweepArgs {
   int K;
@@ -196,7 +214,7 @@ void launch_route(const long long* indptr, const int* indices,
                   int wcap, const float* sumF, int K, int* epre, int* bound,
                   unsigned char* cls, int* tcount, int* tbase, int* totals,
                   float* GG, int* by_class, int qcap, int* pscr, int* wsplit,
-                  hipStream_t stream);
+                  int* zscr, int zero, hipStream_t stream);
 // LDS bytes of a KFW / KFP workgroup: the host clamps wcap / qcap with them
 long long kfw_lds_bytes(int bf16, int K, int wcap);
 long long kfp_lds_bytes(int bf16, int K, int qcap);
@@ -209,6 +227,10 @@ void launch_kfw(const SweepArgs& a, int bf16, int blk0, const int* pos,
 // KFP over the pack positions pos[0 .. n_pack), four per workgroup
 void launch_kfp(const SweepArgs& a, int bf16, const int* pos, int n_pack,
                 int qcap, int skip, hipStream_t stream);
+// kz_fill over the zero segment pos[0 .. n_zero): llh / best of the
+// degree's representative (zrep_node[0 .. KFP_DEG]), gcount = 0
+void launch_kz_fill(const SweepArgs& a, const int* pos, int n_zero,
+                    const int* zrep_node, hipStream_t stream);
 // commit of a routed order laid out [block | wave] (K3S / K3W)
 int k3w_group();
 void launch_k3s(void* F, int bf16, const int* order, int n_block,

@@ -284,6 +284,9 @@ def sparse_sweep_part(
     wsplit: torch.Tensor = None,
     n_pack: int = 0,
     skip: bool = True,
+    n_zero: int = 0,
+    n_rep: int = 0,
+    zscr: torch.Tensor = None,
 ):
     """KFS/KFW for the routed (sparse) nodes: the compact gradient pools,
     llh per node, and the Armijo best step.  ``order_sparse[:n_block]``
@@ -299,7 +302,12 @@ def sparse_sweep_part(
     ``wsplit[:n_pack]`` four nodes per wave (KFP), the rest one wave per
     node; the outputs are bitwise the same either way.  ``skip`` selects
     the KFW/KFP builds that pass over empty edges and empty active sets
-    (``ShardState.sparse_skip``); again bitwise the same outputs."""
+    (``ShardState.sparse_skip``); again bitwise the same outputs.  With
+    ``n_zero > 0`` the packed part of ``wsplit`` holds ``n_pack + n_zero``
+    nodes, which ``zscr`` lists again as [bound > 0 | bound 0]; the latter,
+    the zero class, is not run node by node: KFP runs its ``n_rep``
+    representatives and ``kz_fill`` copies their llh and step to the rest,
+    bitwise the same once more."""
     ext = ensure_loaded()
     dev = F.device
     n_s = int(order_sparse.numel())
@@ -317,6 +325,7 @@ def sparse_sweep_part(
         epre, bound, goffset, gidx, gval, gcount, llh_out, GG, _ladder(cfg, dev),
         best_out, cap, cfg.alpha, cfg.min_p, cfg.max_p, cfg.min_f, cfg.max_f,
         int(n_block), int(wcap), int(qcap), wsplit, int(n_pack), bool(skip),
+        int(n_zero), int(n_rep), zscr,
     )
     return {
         "order": order_sparse,
