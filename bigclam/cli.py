@@ -11,6 +11,9 @@ reference's defaults.
              --holdout FRAC: the K with the highest held-out likelihood)
   extract    re-extract communities from a checkpoint
   eval       score a detected cover against a ground-truth cover
+  score      per-community structural scores of a cover on its graph
+             (conductance, density, Flake-ODF, FOMD, ...; no truth needed;
+             fit --community-scores OUT.tsv does it for the fitted model)
   bench      one timed sweep loop (see also bench.py at the repo root)
 """
 from __future__ import annotations
@@ -185,6 +188,26 @@ def _cmd_eval(args) -> int:
     return 0
 
 
+def _cmd_score(args) -> int:
+    from .engine.scores import (
+        community_scores,
+        summary,
+        write_per_community,
+        write_per_member,
+    )
+    from .io import Cover, read_cover_lines
+
+    g = _load(argparse.Namespace(edgelist=args.graph))
+    cover = Cover.from_raw_members(read_cover_lines(args.cover), g.raw_ids)
+    res = community_scores(g, cover, device=args.device)
+    if args.per_community:
+        write_per_community(args.per_community, res)
+    if args.per_member:
+        write_per_member(args.per_member, res, cover, g.raw_ids)
+    print(json.dumps(dict(summary(res), nodes_dropped=int(cover.dropped))))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(
         prog="bigclam",
@@ -212,6 +235,16 @@ def main(argv=None):
         help="ground-truth cover file (one community per line); adds the "
         "average best-match F1/Jaccard to the result.  'planted' = the "
         "planted:<...> generator's own truth",
+    )
+
+    p_fit.add_argument(
+        "--community-scores",
+        metavar="OUT.tsv",
+        default=None,
+        help="write the per-community structural scores of the fitted "
+        "communities (conductance, internal density, expansion, cut ratio, "
+        "Flake-ODF, FOMD) on the fitted graph and add their summary to the "
+        "result",
     )
 
     p_sel = sub.add_parser(
@@ -247,6 +280,17 @@ def main(argv=None):
     p_eval.add_argument("--device", default=None, help="cuda|cpu (auto)")
     p_eval.add_argument("--per-community", metavar="OUT.tsv", default=None)
 
+    p_score = sub.add_parser(
+        "score", help="per-community structural scores of a cover on its "
+        "graph: conductance, internal density, expansion, cut ratio, "
+        "Flake-ODF, FOMD")
+    p_score.add_argument("cover", help="cover file (fit --out or SNAP cmty)")
+    p_score.add_argument(
+        "graph", help="edge list, or planted:/rmat:/shaped: as for fit")
+    p_score.add_argument("--device", default=None, help="cuda|cpu (auto)")
+    p_score.add_argument("--per-community", metavar="OUT.tsv", default=None)
+    p_score.add_argument("--per-member", metavar="OUT.tsv", default=None)
+
     sub.add_parser(
         "bench",
         help="flagship benchmark (forwards to bench.py)",
@@ -277,6 +321,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.cmd == "eval":
         return _cmd_eval(args)
+    if args.cmd == "score":
+        return _cmd_score(args)
     holdout = getattr(args, "holdout", None)
     if holdout is not None and getattr(args, "resume", None):
         raise SystemExit(
@@ -337,7 +383,8 @@ def main(argv=None):
         save_shard_checkpoint(cfg.checkpoint_dir, tr, res.sweeps, res.llh)
     truth = _truth_cover(args, g)
     scores = {}
-    if cfg.out or truth is not None:
+    cs_path = getattr(args, "community_scores", None)
+    if cfg.out or truth is not None or cs_path:
         # sharded K7: per-rank device-side threshold, compacted lists to
         # rank 0 — no N×K gather; one extraction serves
         # both the output file and the ground-truth evaluation
@@ -361,6 +408,20 @@ def main(argv=None):
             }
             metrics.log(dict(scores, note="truth_eval",
                              truth_nodes_dropped=ev["truth_nodes_dropped"]))
+        if rank == 0 and cs_path:
+            # scored on the graph the model was fitted on (with --holdout:
+            # the train graph)
+            from .engine.scores import (
+                score_pairs,
+                summary as score_summary,
+                write_per_community as write_community_scores,
+            )
+
+            cs = score_pairs(pairs, tr)
+            write_community_scores(cs_path, cs)
+            cs_sum = score_summary(cs)
+            metrics.log(dict(cs_sum, note="community_scores"))
+            scores.update(cs_sum)
     if split is not None:
         from .engine.holdout import heldout_metrics
 

@@ -75,6 +75,13 @@ extern "C" void launch_k8_cover_match(const long long*, const int*,
                                       long long, int, int, int*, int*,
                                       hipStream_t);
 extern "C" int k8_max_tile();
+extern "C" void launch_k10_community_scores(const long long*, const int*,
+                                            const long long*, const int*,
+                                            int, long long, int, long long,
+                                            int, int, int*, long long*,
+                                            long long*, int*, int*,
+                                            hipStream_t);
+extern "C" int k10_max_tile();
 extern "C" void launch_k9_pair_dot(const void*, const void*, int, const int*,
                                    const int*, float*, long long, int, int,
                                    int, hipStream_t);
@@ -894,6 +901,61 @@ void cover_best_match(torch::Tensor grp_ptr, torch::Tensor grp_nodes,
                         current_stream());
 }
 
+// K10: per-community integer edge counts of a cover on a graph (see
+// k10_community_scores in score_kernels.hip).  The cover is group-major
+// (grp_ptr/grp_nodes, ascending per community), the graph a symmetric CSR;
+// dmed = floor(median degree) from the host.
+void community_scores(torch::Tensor grp_ptr, torch::Tensor grp_nodes,
+                      torch::Tensor indptr, torch::Tensor indices,
+                      int64_t dmed, int64_t tile, torch::Tensor int_deg,
+                      torch::Tensor vol, torch::Tensor m2,
+                      torch::Tensor n_flake, torch::Tensor n_fomd) {
+  CHECK_IN(grp_ptr, torch::kInt64);
+  CHECK_IN(grp_nodes, torch::kInt32);
+  CHECK_IN(indptr, torch::kInt64);
+  CHECK_IN(indices, torch::kInt32);
+  CHECK_IN(int_deg, torch::kInt32);
+  CHECK_IN(vol, torch::kInt64);
+  CHECK_IN(m2, torch::kInt64);
+  CHECK_IN(n_flake, torch::kInt32);
+  CHECK_IN(n_fomd, torch::kInt32);
+  const auto dev = grp_ptr.device();
+  TORCH_CHECK(grp_nodes.device() == dev && indptr.device() == dev &&
+                  indices.device() == dev && int_deg.device() == dev &&
+                  vol.device() == dev && m2.device() == dev &&
+                  n_flake.device() == dev && n_fomd.device() == dev,
+              "all tensors must be on the same device");
+  TORCH_CHECK(grp_ptr.dim() == 1 && grp_ptr.size(0) >= 1,
+              "grp_ptr must be [G+1]");
+  TORCH_CHECK(indptr.dim() == 1 && indptr.size(0) >= 1,
+              "indptr must be [N+1]");
+  TORCH_CHECK(grp_nodes.dim() == 1 && indices.dim() == 1,
+              "grp_nodes and indices must be 1-D");
+  TORCH_CHECK(tile >= 1 && tile <= k10_max_tile(), "tile must be in [1, ",
+              k10_max_tile(), "], got ", tile);
+  const int64_t G = grp_ptr.size(0) - 1;
+  const int64_t N = indptr.size(0) - 1;
+  const int64_t M = grp_nodes.size(0);
+  TORCH_CHECK(N < (int64_t(1) << 31), "N must be < 2^31");
+  TORCH_CHECK(G < (int64_t(1) << 31), "community count must be < 2^31");
+  TORCH_CHECK(dmed >= 0 && dmed < (int64_t(1) << 31), "dmed out of range");
+  TORCH_CHECK(int_deg.dim() == 1 && int_deg.size(0) == M,
+              "int_deg must be [M]");
+  TORCH_CHECK(vol.dim() == 1 && vol.size(0) == G && m2.dim() == 1 &&
+                  m2.size(0) == G && n_flake.dim() == 1 &&
+                  n_flake.size(0) == G && n_fomd.dim() == 1 &&
+                  n_fomd.size(0) == G,
+              "vol/m2/n_flake/n_fomd must be [G]");
+  launch_k10_community_scores(
+      i64p(grp_ptr), grp_nodes.data_ptr<int>(), i64p(indptr),
+      indices.data_ptr<int>(), (int)G, (long long)M, (int)N,
+      (long long)indices.size(0), (int)dmed, (int)tile,
+      int_deg.data_ptr<int>(),
+      reinterpret_cast<long long*>(vol.data_ptr<int64_t>()),
+      reinterpret_cast<long long*>(m2.data_ptr<int64_t>()),
+      n_flake.data_ptr<int>(), n_fomd.data_ptr<int>(), current_stream());
+}
+
 // K9: x[i] = F[pu[i]] . F[pv[i]] over the row space [F_own ; F_extra]
 // (index < n_own reads F_own, otherwise F_extra[index - n_own]; see
 // k9_pair_dot_t in pair_kernels.hip).  The index range is verified here,
@@ -1069,6 +1131,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K8: exact best-match (F1/Jaccard argmax) of cover Y per community "
         "of cover X, tiled LDS intersection histogram");
   m.attr("COVER_MAX_TILE") = k8_max_tile();
+  m.def("community_scores", &community_scores,
+        "K10: per-community integer edge counts (int_deg, vol, m2, n_flake, "
+        "n_fomd) of a cover on a CSR graph, 16-lane group per member, tiled "
+        "LDS membership search");
+  m.attr("SCORE_MAX_TILE") = k10_max_tile();
   m.def("pair_dot", &pair_dot,
         "K9: F row dot products for arbitrary node pairs over the row space "
         "[F_own ; F_extra], one wave per pair, deterministic");

@@ -423,6 +423,50 @@ def cover_best_match(
     return best_idx, best_inter
 
 
+def score_max_tile() -> int:
+    """Compiled maximum of K10's LDS tile (member ids per block)."""
+    return int(ensure_loaded().SCORE_MAX_TILE)
+
+
+def community_scores(
+    grp_ptr: torch.Tensor,
+    grp_nodes: torch.Tensor,
+    indptr: torch.Tensor,
+    indices: torch.Tensor,
+    dmed: int,
+    tile: int = None,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+           torch.Tensor]:
+    """K10: the integer edge counts of every community of a cover
+    (group-major ``grp_ptr``/``grp_nodes``, members ascending) on a
+    symmetric CSR graph (``indptr`` int64 [N+1], ``indices`` int32 [nnz]);
+    ``dmed`` is floor(median degree).  Returns ``(int_deg int32 [M], vol
+    int64 [G], m2 int64 [G], n_flake int32 [G], n_fomd int32 [G])`` on
+    device (ops/cover_cpu.py ``community_scores_cpu`` is the same contract
+    on CPU).  ``tile`` (member ids staged in LDS per pass) defaults to the
+    largest community size, capped at the compiled maximum."""
+    ext = ensure_loaded()
+    g = max(int(grp_ptr.shape[0]) - 1, 0)
+    if tile is None:
+        largest = (
+            int((grp_ptr[1:] - grp_ptr[:-1]).max())
+            if g > 0 and grp_ptr.is_cuda and grp_ptr.dtype == torch.int64
+            else 1
+        )
+        tile = min(int(ext.SCORE_MAX_TILE), max(1, largest))
+    dev = grp_ptr.device
+    int_deg = torch.zeros(grp_nodes.shape[0], device=dev, dtype=torch.int32)
+    vol = torch.empty(g, device=dev, dtype=torch.int64)
+    m2 = torch.empty(g, device=dev, dtype=torch.int64)
+    n_flake = torch.empty(g, device=dev, dtype=torch.int32)
+    n_fomd = torch.empty(g, device=dev, dtype=torch.int32)
+    ext.community_scores(
+        grp_ptr, grp_nodes, indptr, indices, int(dmed), int(tile),
+        int_deg, vol, m2, n_flake, n_fomd,
+    )
+    return int_deg, vol, m2, n_flake, n_fomd
+
+
 def pair_dot(
     F_own: torch.Tensor,
     F_extra: torch.Tensor,

@@ -30,6 +30,7 @@ setup(
                 "bigclam/kernels/bigclam_kernels.hip",
                 "bigclam/kernels/cover_kernels.hip",
                 "bigclam/kernels/pair_kernels.hip",
+                "bigclam/kernels/score_kernels.hip",
             ],
             depends=["bigclam/kernels/sparse_sweep.h"],
             extra_compile_args={
