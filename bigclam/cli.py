@@ -14,6 +14,9 @@ reference's defaults.
   score      per-community structural scores of a cover on its graph
              (conductance, density, Flake-ODF, FOMD, ...; no truth needed;
              fit --community-scores OUT.tsv does it for the fitted model)
+  recommend  top-N most likely missing links per node from a checkpoint
+             (fit --recommend OUT.tsv does it for the fitted model; with
+             --holdout it adds recall@N of the held-out edges)
   bench      one timed sweep loop (see also bench.py at the repo root)
 """
 from __future__ import annotations
@@ -208,6 +211,44 @@ def _cmd_score(args) -> int:
     return 0
 
 
+def _cmd_recommend(args) -> int:
+    from .ckpt.checkpoint import load_full_F
+    from .core.sparse_model import SparseModel
+    from .engine.recommend import recommend, write_recommendations
+
+    g = _load(argparse.Namespace(edgelist=args.graph))
+    F = torch.from_numpy(load_full_F(args.checkpoint_dir))
+    if F.shape[0] != g.num_nodes:
+        raise SystemExit(
+            f"checkpoint has {F.shape[0]} rows, the graph {g.num_nodes} nodes"
+        )
+    queries, dropped = None, 0
+    if args.nodes:
+        with open(args.nodes) as f:
+            raw = np.array([int(l) for l in f.read().split()], dtype=np.int64)
+        at = np.minimum(np.searchsorted(g.raw_ids, raw), g.num_nodes - 1)
+        known = g.raw_ids[at] == raw
+        dropped = int((~known).sum())
+        queries = at[known].astype(np.int32)
+    res = recommend(
+        g, SparseModel.from_F(F), queries=queries, n=args.top,
+        device=args.device, max_community_size=args.max_community_size,
+    )
+    write_recommendations(args.out, res, g.raw_ids)
+    print(json.dumps({
+        "queries": int(len(res["queries"])),
+        "n": res["n"],
+        "exact_frac": res["exact_frac"],
+        "work": res["work"],
+        "columns_dropped": res["columns_dropped"],
+        "nodes_dropped": dropped,
+        "mean_n_cand": (
+            float(res["n_cand"].mean()) if len(res["n_cand"]) else 0.0
+        ),
+    }))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(
         prog="bigclam",
@@ -246,6 +287,17 @@ def main(argv=None):
         "Flake-ODF, FOMD) on the fitted graph and add their summary to the "
         "result",
     )
+
+    p_fit.add_argument(
+        "--recommend",
+        metavar="OUT.tsv",
+        default=None,
+        help="write the top-N most likely missing links of every node under "
+        "the fitted model (node, candidate, score, prob) on the fitted "
+        "graph; with --holdout adds recall@N and hit rate of the held-out "
+        "edges to the result",
+    )
+    p_fit.add_argument("--recommend-top", metavar="N", type=int, default=10)
 
     p_sel = sub.add_parser(
         "select-k", help="model selection over the geometric K grid "
@@ -291,6 +343,23 @@ def main(argv=None):
     p_score.add_argument("--per-community", metavar="OUT.tsv", default=None)
     p_score.add_argument("--per-member", metavar="OUT.tsv", default=None)
 
+    p_rec = sub.add_parser(
+        "recommend", help="top-N most likely missing links per node from a "
+        "checkpoint's model")
+    p_rec.add_argument("checkpoint_dir")
+    p_rec.add_argument(
+        "graph", help="edge list, or planted:/rmat:/shaped: as for fit")
+    p_rec.add_argument("--out", required=True, metavar="OUT.tsv")
+    p_rec.add_argument("--top", metavar="N", type=int, default=10)
+    p_rec.add_argument(
+        "--nodes", metavar="FILE", default=None,
+        help="raw ids to recommend for, one per line (default: all nodes; "
+        "ids not in the graph are dropped and counted)")
+    p_rec.add_argument(
+        "--max-community-size", metavar="M", type=int, default=None,
+        help="ignore communities with more than M members")
+    p_rec.add_argument("--device", default=None, help="cuda|cpu (auto)")
+
     sub.add_parser(
         "bench",
         help="flagship benchmark (forwards to bench.py)",
@@ -323,6 +392,8 @@ def main(argv=None):
         return _cmd_eval(args)
     if args.cmd == "score":
         return _cmd_score(args)
+    if args.cmd == "recommend":
+        return _cmd_recommend(args)
     holdout = getattr(args, "holdout", None)
     if holdout is not None and getattr(args, "resume", None):
         raise SystemExit(
@@ -433,6 +504,33 @@ def main(argv=None):
                 {key: hm[key] for key in ("heldout_llh", "heldout_auc",
                                           "heldout_pos", "heldout_neg")}
             )
+    rec_path = getattr(args, "recommend", None)
+    if rec_path:
+        # on the graph the model was fitted on (with --holdout: the train
+        # graph, so held-out edges are legitimate candidates)
+        from .engine.recommend import (
+            heldout_ranking,
+            recommend_trainer,
+            write_recommendations,
+        )
+
+        rec = recommend_trainer(tr, n=args.recommend_top)  # collective
+        if rank == 0:
+            write_recommendations(rec_path, rec, g.raw_ids)
+            note = {
+                "note": "recommend", "n": rec["n"],
+                "queries": int(len(rec["queries"])),
+                "exact_frac": rec["exact_frac"], "work": rec["work"],
+                "mean_n_cand": float(rec["n_cand"].mean()),
+            }
+            if split is not None:
+                hr = heldout_ranking(rec, split)
+                note.update(hr)
+                scores.update(
+                    {key: hr[key] for key in ("heldout_recall_at_n",
+                                              "heldout_hit_rate")}
+                )
+            metrics.log(note)
     if rank == 0:
         print(
             json.dumps(

@@ -82,6 +82,14 @@ extern "C" void launch_k10_community_scores(const long long*, const int*,
                                             long long*, int*, int*,
                                             hipStream_t);
 extern "C" int k10_max_tile();
+extern "C" void launch_k11_topn_links(
+    const long long*, const int*, const float*, const long long*, const int*,
+    const float*, const long long*, const int*, const int*, const int*,
+    const int*, const long long*, int*, float*, int, int, int, long long,
+    long long, int, int, int, int*, float*, int*, hipStream_t);
+extern "C" int k11_max_n();
+extern "C" int k11_min_slots();
+extern "C" int k11_max_lds_slots();
 extern "C" void launch_k9_pair_dot(const void*, const void*, int, const int*,
                                    const int*, float*, long long, int, int,
                                    int, hipStream_t);
@@ -956,6 +964,109 @@ void community_scores(torch::Tensor grp_ptr, torch::Tensor grp_nodes,
       n_flake.data_ptr<int>(), n_fomd.data_ptr<int>(), current_stream());
 }
 
+// K11: top-n link recommendation for the queries q[sel[*]] from the sparse
+// model (row- and column-major) against the graph's CSR (see k11_topn_links
+// in link_kernels.hip).  One launch: lds_slots > 0 keeps every table in
+// LDS, lds_slots == 0 in the slices tab_off of scratch_keys/scratch_vals.
+// Everything the kernel indexes with is verified here, once per call, from
+// the min/max of the index tensors.
+void topn_links(torch::Tensor row_ptr, torch::Tensor row_col,
+                torch::Tensor row_val, torch::Tensor col_ptr,
+                torch::Tensor col_row, torch::Tensor col_val,
+                torch::Tensor indptr, torch::Tensor indices, torch::Tensor q,
+                torch::Tensor sel, torch::Tensor tab_slots,
+                torch::Tensor tab_off, torch::Tensor scratch_keys,
+                torch::Tensor scratch_vals, int64_t n, int64_t lds_slots,
+                int64_t block, torch::Tensor top_id, torch::Tensor top_score,
+                torch::Tensor n_cand) {
+  CHECK_IN(row_ptr, torch::kInt64);
+  CHECK_IN(row_col, torch::kInt32);
+  CHECK_IN(row_val, torch::kFloat32);
+  CHECK_IN(col_ptr, torch::kInt64);
+  CHECK_IN(col_row, torch::kInt32);
+  CHECK_IN(col_val, torch::kFloat32);
+  CHECK_IN(indptr, torch::kInt64);
+  CHECK_IN(indices, torch::kInt32);
+  CHECK_IN(q, torch::kInt32);
+  CHECK_IN(sel, torch::kInt32);
+  CHECK_IN(tab_slots, torch::kInt32);
+  CHECK_IN(tab_off, torch::kInt64);
+  CHECK_IN(scratch_keys, torch::kInt32);
+  CHECK_IN(scratch_vals, torch::kFloat32);
+  CHECK_IN(top_id, torch::kInt32);
+  CHECK_IN(top_score, torch::kFloat32);
+  CHECK_IN(n_cand, torch::kInt32);
+  const auto dev = row_ptr.device();
+  for (const auto& t :
+       {row_col, row_val, col_ptr, col_row, col_val, indptr, indices, q, sel,
+        tab_slots, tab_off, scratch_keys, scratch_vals, top_id, top_score,
+        n_cand})
+    TORCH_CHECK(t.device() == dev, "all tensors must be on the same device");
+  TORCH_CHECK(n >= 1 && n <= k11_max_n(), "n must be in [1, ", k11_max_n(),
+              "], got ", n);
+  TORCH_CHECK(block == 64 || block == 128 || block == 256,
+              "block must be 64, 128 or 256, got ", block);
+  TORCH_CHECK(lds_slots >= 0 && lds_slots <= k11_max_lds_slots(),
+              "lds_slots must be in [0, ", k11_max_lds_slots(), "], got ",
+              lds_slots);
+  for (const auto& t : {row_ptr, row_col, row_val, col_ptr, col_row, col_val,
+                        indptr, indices, q, sel, tab_slots, tab_off,
+                        scratch_keys, scratch_vals, n_cand})
+    TORCH_CHECK(t.dim() == 1, "index and value arrays must be 1-D");
+  TORCH_CHECK(row_ptr.size(0) >= 1 && indptr.size(0) == row_ptr.size(0),
+              "row_ptr and indptr must both be [N+1]");
+  TORCH_CHECK(col_ptr.size(0) >= 1, "col_ptr must be [K+1]");
+  const int64_t N = row_ptr.size(0) - 1;
+  const int64_t K = col_ptr.size(0) - 1;
+  const int64_t mnnz = row_col.size(0);
+  const int64_t Q = q.size(0);
+  const int64_t Qsel = sel.size(0);
+  TORCH_CHECK(N < (int64_t(1) << 31) && K < (int64_t(1) << 31) &&
+                  Q < (int64_t(1) << 31),
+              "N, K and the query count must be < 2^31");
+  TORCH_CHECK(row_val.size(0) == mnnz && col_row.size(0) == mnnz &&
+                  col_val.size(0) == mnnz,
+              "row_col/row_val/col_row/col_val must all be [nnz]");
+  TORCH_CHECK(tab_slots.size(0) == Qsel, "tab_slots must be [len(sel)]");
+  TORCH_CHECK(lds_slots > 0 || tab_off.size(0) == Qsel,
+              "tab_off must be [len(sel)] for global tables");
+  TORCH_CHECK(scratch_vals.size(0) == scratch_keys.size(0),
+              "scratch_keys and scratch_vals must have one length");
+  TORCH_CHECK(top_id.dim() == 2 && top_id.size(0) == Q && top_id.size(1) == n,
+              "top_id must be [Q, n]");
+  TORCH_CHECK(top_score.dim() == 2 && top_score.size(0) == Q &&
+                  top_score.size(1) == n,
+              "top_score must be [Q, n]");
+  TORCH_CHECK(n_cand.size(0) == Q, "n_cand must be [Q]");
+  if (Qsel == 0) return;
+  TORCH_CHECK(q.min().item<int>() >= 0 && q.max().item<int>() < N,
+              "q out of range [0, N)");
+  TORCH_CHECK(sel.min().item<int>() >= 0 && sel.max().item<int>() < Q,
+              "sel out of range [0, Q)");
+  const int64_t smin = tab_slots.min().item<int>();
+  const int64_t smax = tab_slots.max().item<int>();
+  TORCH_CHECK(smin >= k11_min_slots() &&
+                  tab_slots.bitwise_and(tab_slots - 1).max().item<int>() == 0,
+              "tab_slots must be powers of two >= ", k11_min_slots());
+  if (lds_slots > 0) {
+    TORCH_CHECK(smax <= lds_slots, "a table exceeds lds_slots");
+  } else {
+    TORCH_CHECK(tab_off.min().item<int64_t>() >= 0 &&
+                    (tab_off + tab_slots).max().item<int64_t>() <=
+                        scratch_keys.size(0),
+                "a table slice lies outside the scratch buffer");
+  }
+  launch_k11_topn_links(
+      i64p(row_ptr), row_col.data_ptr<int>(), row_val.data_ptr<float>(),
+      i64p(col_ptr), col_row.data_ptr<int>(), col_val.data_ptr<float>(),
+      i64p(indptr), indices.data_ptr<int>(), q.data_ptr<int>(),
+      sel.data_ptr<int>(), tab_slots.data_ptr<int>(), i64p(tab_off),
+      scratch_keys.data_ptr<int>(), scratch_vals.data_ptr<float>(), (int)Qsel,
+      (int)N, (int)K, (long long)mnnz, (long long)indices.size(0), (int)n,
+      (int)lds_slots, (int)block, top_id.data_ptr<int>(),
+      top_score.data_ptr<float>(), n_cand.data_ptr<int>(), current_stream());
+}
+
 // K9: x[i] = F[pu[i]] . F[pv[i]] over the row space [F_own ; F_extra]
 // (index < n_own reads F_own, otherwise F_extra[index - n_own]; see
 // k9_pair_dot_t in pair_kernels.hip).  The index range is verified here,
@@ -1136,6 +1247,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "n_fomd) of a cover on a CSR graph, 16-lane group per member, tiled "
         "LDS membership search");
   m.attr("SCORE_MAX_TILE") = k10_max_tile();
+  m.def("topn_links", &topn_links,
+        "K11: top-n link recommendation per query node from the sparse "
+        "model, one block per query, open-addressing (id, score) table in "
+        "LDS or global scratch, ordered fp32 accumulation");
+  m.attr("LINK_MAX_N") = k11_max_n();
+  m.attr("LINK_MIN_SLOTS") = k11_min_slots();
+  m.attr("LINK_MAX_LDS_SLOTS") = k11_max_lds_slots();
   m.def("pair_dot", &pair_dot,
         "K9: F row dot products for arbitrary node pairs over the row space "
         "[F_own ; F_extra], one wave per pair, deterministic");

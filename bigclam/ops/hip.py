@@ -483,3 +483,163 @@ def pair_dot(
     x = torch.empty(pu.shape[0], device=F_own.device, dtype=torch.float32)
     ext.pair_dot(F_own, F_extra, pu, pv, x)
     return x
+
+
+def link_max_n() -> int:
+    """Compiled maximum of K11's ``n`` (recommendations per query)."""
+    return int(ensure_loaded().LINK_MAX_N)
+
+
+def _check_link_input(t, name: str, dtype) -> None:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name} must be on GPU")
+    if t.dtype != dtype:
+        raise RuntimeError(f"{name} has wrong dtype ({t.dtype}, not {dtype})")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name} must be contiguous")
+    if t.dim() != 1:
+        raise RuntimeError(f"{name} must be 1-D")
+
+
+def _pow2_at_least(x: torch.Tensor) -> torch.Tensor:
+    """Smallest power of two >= x, elementwise (int64, x >= 1)."""
+    x = x - 1
+    for s in (1, 2, 4, 8, 16, 32):
+        x = x | (x >> s)
+    return x + 1
+
+
+def topn_links(
+    model,
+    indptr: torch.Tensor,
+    indices: torch.Tensor,
+    q: torch.Tensor,
+    n: int,
+    lds_slots: int = None,
+    scratch_bytes: int = 1 << 30,
+    block: int = 256,
+):
+    """K11: for every query node ``q[i]`` (int32, any order, repeats
+    allowed) the ``n`` nodes with the largest ``F_u . F_v`` among the nodes
+    that are not u, not a CSR neighbour of u and share a nonzero column with
+    u.  ``model`` is a ``core.sparse_model.SparseModel`` on the device;
+    ``indptr`` int64 [N+1] / ``indices`` int32 are the graph's symmetric
+    CSR.  Returns ``(top_id int32 [Q, n] padded with -1, top_score float32
+    [Q, n] padded with 0, n_cand int32 [Q], info)`` on device;
+    ops/links_cpu.py ``topn_links_cpu`` is the same contract on CPU and
+    agrees bitwise.
+
+    Every query accumulates in its own (id, score) table of
+    ``pow2 >= 2 * min(T_u, N)`` slots (at least 64), T_u = the summed
+    member counts of u's columns, so a table never fills.  Tables of up to
+    ``lds_slots`` slots (default and maximum: 8192 = 64 KB) live in LDS;
+    the other queries run the same code on slices of a global scratch, in
+    batches of at most ``scratch_bytes``.  ``info`` reports the split:
+    ``n_lds``, ``n_global``, ``global_batches``, ``work`` (sum of T_u) and
+    ``max_slots``."""
+    ext = ensure_loaded()
+    n = int(n)
+    if not 1 <= n <= int(ext.LINK_MAX_N):
+        raise RuntimeError(
+            f"n must be in [1, {int(ext.LINK_MAX_N)}], got {n}"
+        )
+    max_lds = int(ext.LINK_MAX_LDS_SLOTS)
+    min_slots = int(ext.LINK_MIN_SLOTS)
+    lds_slots = max_lds if lds_slots is None else int(lds_slots)
+    if not 0 <= lds_slots <= max_lds:
+        raise RuntimeError(
+            f"lds_slots must be in [0, {max_lds}], got {lds_slots}"
+        )
+    for name, dt in (("row_ptr", torch.int64), ("row_col", torch.int32),
+                     ("row_val", torch.float32), ("col_ptr", torch.int64),
+                     ("col_row", torch.int32), ("col_val", torch.float32)):
+        _check_link_input(getattr(model, name), name, dt)
+    _check_link_input(indptr, "indptr", torch.int64)
+    _check_link_input(indices, "indices", torch.int32)
+    _check_link_input(q, "q", torch.int32)
+    dev = q.device
+    n_nodes, k, nnz = model.n, model.k, int(model.row_col.shape[0])
+    if (model.row_ptr.shape[0] != n_nodes + 1
+            or indptr.shape[0] != n_nodes + 1
+            or model.col_ptr.shape[0] != k + 1
+            or any(getattr(model, f).shape[0] != nnz
+                   for f in ("row_val", "col_row", "col_val"))):
+        raise RuntimeError(
+            "pointer/value array lengths do not match N, K and nnz"
+        )
+    n_q = int(q.shape[0])
+    top_id = torch.full((n_q, n), -1, device=dev, dtype=torch.int32)
+    top_score = torch.zeros((n_q, n), device=dev, dtype=torch.float32)
+    n_cand = torch.zeros(n_q, device=dev, dtype=torch.int32)
+    info = {"n_lds": 0, "n_global": 0, "global_batches": 0, "work": 0,
+            "max_slots": 0}
+    if n_q == 0:
+        return top_id, top_score, n_cand, info
+    if int(q.min()) < 0 or int(q.max()) >= n_nodes:
+        raise RuntimeError(f"q out of range [0, {n_nodes})")
+    if nnz and (int(model.row_col.min()) < 0 or int(model.row_col.max()) >= k
+                or int(model.row_ptr[-1]) != nnz
+                or int(model.col_ptr[-1]) != nnz):
+        raise RuntimeError("malformed sparse model")
+
+    # exact candidate bound T_u per query (cold path)
+    sizes = model.col_ptr[1:] - model.col_ptr[:-1]
+    cum = torch.zeros(nnz + 1, device=dev, dtype=torch.int64)
+    torch.cumsum(sizes[model.row_col.long()], 0, out=cum[1:])
+    ql = q.long()
+    bound = cum[model.row_ptr[ql + 1]] - cum[model.row_ptr[ql]]
+    slots = _pow2_at_least(
+        (2 * bound.clamp(max=n_nodes)).clamp(min=min_slots)
+    )
+    info["work"] = int(bound.sum())
+    info["max_slots"] = int(slots.max())
+    if info["max_slots"] > 1 << 30:
+        raise RuntimeError("a candidate table needs more than 2^30 slots")
+
+    arrays = (model.row_ptr, model.row_col, model.row_val, model.col_ptr,
+              model.col_row, model.col_val, indptr, indices, q)
+    no_off = torch.empty(0, device=dev, dtype=torch.int64)
+    no_keys = torch.empty(0, device=dev, dtype=torch.int32)
+    no_vals = torch.empty(0, device=dev, dtype=torch.float32)
+
+    # LDS tables: small ones apart, so one heavy query does not size the
+    # dynamic LDS (and the occupancy) of every block
+    in_lds = slots <= lds_slots
+    for part in (in_lds & (slots <= 1024), in_lds & (slots > 1024)):
+        sel = torch.nonzero(part).flatten().to(torch.int32)
+        if sel.numel() == 0:
+            continue
+        tab = slots[part].to(torch.int32)
+        ext.topn_links(*arrays, sel, tab, no_off, no_keys, no_vals, n,
+                       int(tab.max()), int(block), top_id, top_score, n_cand)
+        info["n_lds"] += int(sel.numel())
+
+    # global tables, batched under the scratch budget
+    sel_g = torch.nonzero(~in_lds).flatten()
+    if sel_g.numel():
+        budget = int(scratch_bytes) // 8  # slots: int32 id + fp32 score
+        tab_g = slots[sel_g]
+        if int(tab_g.max()) > budget:
+            raise RuntimeError(
+                f"a candidate table of {int(tab_g.max())} slots does not fit "
+                f"scratch_bytes = {int(scratch_bytes)}"
+            )
+        ends = torch.cumsum(tab_g, 0).cpu().numpy()
+        cuts, start, base = [], 0, 0
+        while start < len(ends):  # greedy: as many tables as fit
+            stop = int(ends.searchsorted(base + budget, side="right"))
+            cuts.append((start, stop))
+            start, base = stop, int(ends[stop - 1])
+        largest = max(int(ends[b - 1]) - (int(ends[a - 1]) if a else 0)
+                      for a, b in cuts)
+        keys = torch.empty(largest, device=dev, dtype=torch.int32)
+        vals = torch.empty(largest, device=dev, dtype=torch.float32)
+        for a, b in cuts:
+            tab = tab_g[a:b]
+            off = torch.cumsum(tab, 0) - tab
+            ext.topn_links(*arrays, sel_g[a:b].to(torch.int32),
+                           tab.to(torch.int32), off.contiguous(), keys, vals,
+                           n, 0, int(block), top_id, top_score, n_cand)
+        info["n_global"] = int(sel_g.numel())
+        info["global_batches"] = len(cuts)
+    return top_id, top_score, n_cand, info

@@ -31,6 +31,7 @@ setup(
                 "bigclam/kernels/cover_kernels.hip",
                 "bigclam/kernels/pair_kernels.hip",
                 "bigclam/kernels/score_kernels.hip",
+                "bigclam/kernels/link_kernels.hip",
             ],
             depends=["bigclam/kernels/sparse_sweep.h"],
             extra_compile_args={
